@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: clips/s of the SlowFast-R50 (+TxEncoder) hot path on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload ...]
+    python bench.py --gpus N --steps K --warmup W [--workload ...] [--dump-outputs DIR] [--full]
 
 For N > 1 the driver launches one rank per GPU through torch.distributed.run (RCCL);
 clips are sharded across ranks (8 per GPU, weak scaling), the only collective is the
@@ -19,6 +19,12 @@ Beside the headline value the N = 1 train line carries two more measured legs (r
 `feat_fwd` = configs[1] (eval forward, BN shifts calibrated for the bf16 weight rounding on two other clips: the
 arithmetic whose logits sit within 1e-3 of the fp32 oracle, `config.parity`) and `canonical_b8x5` = the reference's own
 batch, 8 videos x 5 events = 40 clips per step.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line (`roofline` and
+`cpu_baseline` are null, the two extra legs absent).  `--full` adds everything above (`--no-roofline`,
+`--no-cpu-baseline`, `--no-feat-fwd` then drop single parts).  `--dump-outputs DIR` writes what the timed path computed
+in its last step as DIR/<name>.npy (float32 / float64, a fixed seeded sample of the parameter-sized arrays), right after
+the timed region: the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -68,11 +74,47 @@ def parse():
     ap.add_argument("--clips-per-gpu", type=int, default=8,
                     help="PROBE ONLY: clips per GPU other than the BASELINE config's 8 (multiple of 4); the line is "
                          "marked config.probe and is not the headline metric")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the instrumented roofline pass, the CPU baseline and (train) the "
+                         "`feat_fwd` / `canonical_b8x5` legs; off by default")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the instrumented roofline pass")
     ap.add_argument("--no-feat-fwd", action="store_true",
-                    help="train workload: skip the feature-extractor forward leg (`feat_fwd` object of the line)")
+                    help="with --full, train workload: skip the feature-extractor forward leg (`feat_fwd` object of the "
+                         "line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (rank 0)")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 21  # elements of a parameter-sized array that are written: a fixed, seeded sample
+
+
+def dump_outputs(dirname, arrays):
+    """arrays: name -> tensor / array / list.  Written as float32 (float64 for integer data such as token ids and
+    indices, exact below 2^53); at most DUMP_MAX_BYTES in all."""
+    import numpy as np
+
+    out = {}
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().float().cpu().numpy() if a.is_floating_point() else a.detach().cpu().numpy()
+        a = np.asarray(a)
+        out[name] = a.astype(np.float32 if a.dtype.kind == "f" and a.dtype.itemsize <= 4 else np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes > {DUMP_MAX_BYTES}"
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def sample_index(n, k=DUMP_SAMPLE):
+    """A fixed, seeded, sorted sample of k of n positions (all of them when n <= k)."""
+    if n <= k:
+        return torch.arange(n)
+    g = torch.Generator().manual_seed(0)
+    return torch.randint(0, n, (k,), generator=g).sort().values
 
 
 def _v(a):
@@ -434,6 +476,14 @@ def bench_srl_gen(args, rank, world, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     ntok = sum(len(v["tokens"]) for r in out for v in r["vb_output"].values())
+    if rank == 0 and args.dump_outputs:
+        # the caller receives one token sequence per event (pad-filled to one length; -1 pads a shorter one)
+        seqs = [v["tokens"] for r in out for v in r["vb_output"].values()]
+        width = max(len(t) for t in seqs)
+        toks = torch.full((len(seqs), width), -1, dtype=torch.int64)
+        for i, t in enumerate(seqs):
+            toks[i, :len(t)] = torch.tensor(t, dtype=torch.int64)
+        dump_outputs(args.dump_outputs, {"tokens": toks.view(len(out), -1, width)})
     if rank == 0:
         emit(({
             "metric": f"clips/s SRL caption generation, beam 5 x {max_len} tokens, {dec} decoder",
@@ -699,13 +749,15 @@ def main():
                 out = step()
         used_graph = True
 
+    last = {"out": None if ts is not None else out}
+
     def run_once():
         if ts is not None:
             ts.run()
         elif graph is not None:
-            graph.replay()
+            graph.replay()  # `out` is the graph's output tensor, rewritten by every replay
         else:
-            step()
+            last["out"] = step()
 
     if used_graph:
         for _ in range(max(args.warmup - n_eager, 1)):
@@ -732,8 +784,19 @@ def main():
     value = clips / dt
     flop_per_clip = GFLOP_PER_CLIP_FWD * (3.0 if train else 1.0)
 
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's results, before any later pass touches them: the training step hands its caller the
+        # loss and the updated parameters (with the gradients they were updated from); the forward, the head's output
+        if ts is not None:
+            idx = sample_index(ts.arena.numel)
+            di = idx.to(dev)
+            dump_outputs(args.dump_outputs, {"loss": ts.loss.reshape(1), "params_sample": ts.arena.data[di],
+                                             "grads_sample": ts.arena.grad[di], "sample_index": idx})
+        else:
+            dump_outputs(args.dump_outputs, {"head_out": last["out"]})
+
     roof = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         if ts is not None:
             ts.collectives = False  # the rank-0-only instrumented pass must not enter a collective
         # per-kernel durations are taken with every launch on ONE stream (the timed region runs the
@@ -858,13 +921,13 @@ def main():
     # driver-measured number too.  Not part of `value`.
     fwd = None
     canon = None
-    if rank == 0 and train and args.graph and not args.no_feat_fwd:
+    if rank == 0 and train and args.graph and args.full and not args.no_feat_fwd:
         fwd = feat_fwd_leg(dev, rank)
         if world == 1 and CLIPS_PER_GPU == 8:
             canon = canonical_b8x5_leg(dev, rank)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # a reported baseline of the N = 1 line only
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:  # a reported baseline of the N = 1 line only
         cpu = cpu_baseline(args.workload, len(comm.vb_id_vocab))
 
     if rank == 0:

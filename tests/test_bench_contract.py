@@ -104,3 +104,33 @@ def test_forward_line_and_cli_surface():
     for env in ("RANK", "LOCAL_RANK"):
         assert f'os.environ.get("{env}"' in src, env
     assert "dist_launch.world_from_env(args.gpus)" in src  # --gpus is reconciled with WORLD_SIZE, never ignored
+
+
+def test_full_and_dump_outputs_cli_surface(tmp_path):
+    """A plain run times only its steps: the instrumented roofline pass, the CPU baseline and the extra legs sit behind
+    --full; --dump-outputs writes float32 / float64 .npy files within 64 MB, the parameter-sized ones as a fixed sample."""
+    import sys
+
+    import numpy as np
+    import pytest
+    import torch
+
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert 'add_argument("--full", action="store_true"' in src and 'add_argument("--dump-outputs"' in src
+    assert "args.full and not args.no_roofline" in src and "args.full and not args.no_cpu_baseline" in src
+    assert "args.full and not args.no_feat_fwd" in src
+    sys.path.insert(0, ROOT)
+    import bench
+
+    a, b = bench.sample_index(10 ** 8), bench.sample_index(10 ** 8)
+    assert torch.equal(a, b) and a.numel() == bench.DUMP_SAMPLE and bool((a[1:] >= a[:-1]).all()) and int(a[-1]) < 10 ** 8
+    assert torch.equal(bench.sample_index(5), torch.arange(5))
+    bench.dump_outputs(str(tmp_path / "d"), {"x": torch.ones(3, 2, dtype=torch.bfloat16), "i": torch.arange(4),
+                                             "y": np.zeros(2, np.float64)})
+    got = {f: np.load(tmp_path / "d" / f) for f in sorted(os.listdir(tmp_path / "d"))}
+    assert {k: v.dtype for k, v in got.items()} == {"i.npy": np.float64, "x.npy": np.float32, "y.npy": np.float64}
+    assert got["x.npy"].shape == (3, 2) and got["i.npy"].tolist() == [0, 1, 2, 3]
+    big = torch.zeros((bench.DUMP_MAX_BYTES // 4) + 1)
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "e"), {"big": big})
+    assert not os.path.exists(tmp_path / "e")

@@ -93,7 +93,7 @@ def test_bench_two_ranks_sharing_the_gpu_runs_the_whole_n_gt_1_path(dev):
     Exercises what the driver's scaling run will execute on 2 / 4 / 8 GPUs: parameter broadcast, the five segment graphs
     with a bf16 bucket all-reduce behind each, barriers on both sides of the timed region, max over ranks, rank 0's
     instrumented pass while rank 1 waits, ONE JSON line.  The throughput of two ranks sharing a chip means nothing."""
-    rc, out, err = _run(["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"],
+    rc, out, err = _run(["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline"],
                         {"VS_BENCH_SHARE_GPU": "1", "VS_BENCH_DIST_BACKEND": "gloo"}, timeout=1500)
     assert rc == 0, out[-2000:] + err
     lines = out.strip().splitlines()
@@ -104,6 +104,37 @@ def test_bench_two_ranks_sharing_the_gpu_runs_the_whole_n_gt_1_path(dev):
     ga = line["config"]["grad_allreduce"]
     assert "4 bucket" in ga and "bf16" in ga and "overlapped" in ga, ga
     assert line["cpu_baseline"] is None and line["roofline"] is not None
+
+
+@pytest.mark.parametrize("workload", ["sf_txenc_train", "feat_fwd"])
+def test_plain_bench_times_only_its_steps_and_dumps_the_last_one(workload, dev, tmp_path):
+    """A plain run (no --full): the headline fields, exactly --steps timed steps, no roofline / CPU baseline / extra legs;
+    --dump-outputs writes the last timed step's results as float32 / float64 .npy files, 64 MB at most."""
+    import numpy as np
+
+    rc, out, err = _run(["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2", "--workload", workload,
+                         "--dump-outputs", str(tmp_path / "out")])
+    assert rc == 0, out[-2000:] + err
+    lines = out.strip().splitlines()
+    assert len(lines) == 1, out
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 2 and line["unit"] == "clips/s" and line["dtype"] == "bf16"
+    assert line["higher_is_better"] is True and line["ms_per_step"] > 0
+    assert abs(line["value"] - 8 / (line["ms_per_step"] * 1e-3)) < 0.02 * line["value"]
+    assert line["roofline"] is None and line["cpu_baseline"] is None
+    assert "feat_fwd" not in line and "canonical_b8x5" not in line
+    files = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    want = {"loss", "params_sample", "grads_sample", "sample_index"} if workload == "sf_txenc_train" else {"head_out"}
+    assert set(files) == want
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    for name, a in files.items():
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all(), name
+    if workload == "sf_txenc_train":
+        n = files["sample_index"].size
+        assert files["params_sample"].shape == files["grads_sample"].shape == (n,) and files["loss"].shape == (1,)
+        assert np.all(np.diff(files["sample_index"]) >= 0) and np.any(files["grads_sample"] != 0)
+    else:
+        assert files["head_out"].shape[0] == 8
 
 
 def test_feat_extractor_cli_from_a_trained_checkpoint_and_from_a_caffe2_pickle(dev, tmp_path):

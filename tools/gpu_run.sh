@@ -12,10 +12,10 @@ tail -n 60 $OUT/pytest_gpu.log
 echo "== smoke"
 timeout 600 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1; echo "smoke exit $?" | tee -a $OUT/smoke.log; tail -n 5 $OUT/smoke.log
 echo "== bench feat_fwd"
-timeout 900 python bench.py --steps 10 --warmup 3 --workload feat_fwd > $OUT/bench_feat_fwd.log 2>&1; echo "bench exit $?" | tee -a $OUT/bench_feat_fwd.log; tail -n 4 $OUT/bench_feat_fwd.log
+timeout 900 python bench.py --full --steps 10 --warmup 3 --workload feat_fwd > $OUT/bench_feat_fwd.log 2>&1; echo "bench exit $?" | tee -a $OUT/bench_feat_fwd.log; tail -n 4 $OUT/bench_feat_fwd.log
 if [ "${RUN_TRAIN:-0}" = "1" ]; then
   echo "== bench train"
-  timeout 900 python bench.py --steps 5 --warmup 2 --workload sf_txenc_train > $OUT/bench_train.log 2>&1; echo "bench exit $?" | tee -a $OUT/bench_train.log; tail -n 4 $OUT/bench_train.log
+  timeout 900 python bench.py --full --steps 5 --warmup 2 --workload sf_txenc_train > $OUT/bench_train.log 2>&1; echo "bench exit $?" | tee -a $OUT/bench_train.log; tail -n 4 $OUT/bench_train.log
 fi
 if [ "${RUN_PROF:-1}" = "1" ]; then
   echo "== rocprof"

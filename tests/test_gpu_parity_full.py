@@ -255,6 +255,14 @@ def _block_as_the_kernels_compute_it(blk, x):
                                                     ("slowfast", 50, 224, 1, (2, 3)), ("slowfast", 50, 224, 8, (4, 5)),
                                                     ("slowfast", 50, 224, 8, (2, 3))])
 def test_every_resblock_fwd_bwd_matches_oracle_on_the_oracles_own_tensors(arch, depth, hw, n, stages, dev, monkeypatch):
+    threads0 = torch.get_num_threads()
+    try:
+        _every_resblock_case(arch, depth, hw, n, stages, dev, monkeypatch)
+    finally:  # (also when an assertion fails mid-test: the next tests must not inherit the 16-thread setting)
+        torch.set_num_threads(threads0)
+
+
+def _every_resblock_case(arch, depth, hw, n, stages, dev, monkeypatch):
     import copy
     import os
 
@@ -263,7 +271,6 @@ def test_every_resblock_fwd_bwd_matches_oracle_on_the_oracles_own_tensors(arch, 
     from vidsitu_amd.trunk import ResBlock, VideoTrunk
 
     bench_batch = hw >= 224 and n >= 8
-    threads0 = torch.get_num_threads()
     if bench_batch:  # the GPU box's 256 hardware threads are ~50x slower than 16 on this oracle
         torch.set_num_threads(min(16, os.cpu_count() or 16))
     group_calls, unit_calls = [], []
@@ -357,7 +364,6 @@ def test_every_resblock_fwd_bwd_matches_oracle_on_the_oracles_own_tensors(arch, 
         for args in pending:
             compare(*args)
         pending = []
-    torch.set_num_threads(threads0)
     print(f"grouped weight-gradient launches (items each): {group_calls}; per-unit launches: {len(unit_calls)}")
     if bench_batch and stages == (4, 5):
         # slow res4 (6 blocks: 3 + 3) and res5 (3 blocks) leave as three-block groups: 3 launches of >= 9 items, and no
@@ -386,10 +392,11 @@ def test_every_resblock_fwd_bwd_matches_oracle_on_the_oracles_own_tensors(arch, 
     # 100 352 positions, a post-ReLU / max-pool tensor with a large mean) against an output gradient that sums to zero
     # per channel are cancellation-dominated; the operands of the two sides differ by their own bf16 roundings and the
     # sums move by 7-9 % (round 3).  The kernel itself is exact on equal operands at that shape: 2-7e-7 against fp64,
-    # asserted at <= 5e-6 by tests/test_gpu_conv.py::test_wgrad_vs_fp64_on_equal_bf16_operands_at_fast_res0_shapes (and
-    # the BN-backward sums at 802 816 positions by tests/test_gpu_bn_pool.py::
-    # test_bn_backward_sums_vs_fp64_on_equal_operands_at_full_size) -- THAT is the bound a wrong kernel fails; the
-    # 1.5e-1 these two tensors get here only says "nothing gross", everything else gets 4e-2.
+    # asserted at <= 5e-6 by tests/test_gpu_conv_bench_shapes.py (every convolution of the step at the bench batch, all
+    # three directions, the grouped launches included) and by tests/test_gpu_conv.py::
+    # test_wgrad_vs_fp64_on_equal_bf16_operands_at_fast_res0_shapes (and the BN-backward sums at 802 816 positions by
+    # tests/test_gpu_bn_pool.py::test_bn_backward_sums_vs_fp64_on_equal_operands_at_full_size) -- THAT is the bound a
+    # wrong kernel fails; the 1.5e-1 these two tensors get here only says "nothing gross", everything else gets 4e-2.
     # Round 4: the reduction order of the wide multi-tap convolutions became chunk-major (ConvP::korder) -- another
     # draw of the same process: at the 64-pixel crop one BN-bias gradient of slow s4 (256 positions per channel, half of
     # them behind the mask) moved from < 1.4e-2 to 4.9e-2 (its block's dx 2.3e-2) while the table's median and the
@@ -402,8 +409,9 @@ def test_every_resblock_fwd_bwd_matches_oracle_on_the_oracles_own_tensors(arch, 
             return 1.5e-1
         # stages 2 / 3 at the bench batch (round 6): the fast pathway's res2 blocks sum 8-channel tensors over 6.4 million
         # positions -- every parameter gradient there is a cancellation-dominated sum of the class described above
-        # (measured: b_bn bias / weight of s2.pathway1_res1 1.0e-1 / 6.6e-2); the kernels are held to fp64 on equal
-        # operands at that size by tests/test_gpu_bn_pool.py and tests/test_gpu_conv.py
+        # (measured: b_bn bias / weight of s2.pathway1_res1 1.0e-1 / 6.6e-2); the convolution kernels are held to fp64 on
+        # equal operands at that size, layer by layer and direction by direction, by tests/test_gpu_conv_bench_shapes.py,
+        # the BN-backward sums by tests/test_gpu_bn_pool.py
         if bench_batch and stages == (2, 3) and block.startswith("s2.pathway1_"):
             return 1.5e-1
         # (the relaxed bound is for the ONE tensor that moved -- slow s4 res2's b_bn bias at the 64-pixel crop,
@@ -422,7 +430,6 @@ def test_every_resblock_fwd_bwd_matches_oracle_on_the_oracles_own_tensors(arch, 
         # res3: the launches the step runs) entirely within 2e-2 (measured: 7.6e-3 .. 1.1e-2).
         s3_slow = [(e, n) for e, n, *_ in worst if n.startswith("s3.pathway0_")]
         assert len(s3_slow) == 4 and all(e < 2e-2 for e, _ in s3_slow), f"grouped slow res3 blocks: {s3_slow}"
-        torch.set_num_threads(threads0)
         return
     assert errs[len(errs) // 2] < 1e-2, f"median block's worst tensor {errs[len(errs) // 2]:.3e}"
     tight = sum(1 for e in errs if e < 1e-2)

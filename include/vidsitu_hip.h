@@ -531,6 +531,21 @@ int vs_resize_bicubic_u8(const uint8_t* src, uint8_t* dst, uint8_t* tmp, int64_t
                          int Ho, int Wo, const int32_t* bounds_h, const int32_t* kk_h, int ksize_h,
                          const int32_t* bounds_v, const int32_t* kk_v, int ksize_v, int y0, int y1,
                          void* stream);
+/* Fused ingest: ONE launch from decoded frames to both pathways' stem inputs.  src u8 [N][T][H0][W0][3]
+ * -> y_fast bf16 [N][T][Ho][Wo][cpad_fast] and, when Tslow > 0, y_slow bf16 [N][Tslow][Ho][Wo][cpad_slow]
+ * holding the frames t_index_slow[Tslow] (device, int32) selects (a selected frame is written to both).
+ * Exactly the bits of vs_resize_bicubic_u8 followed by one vs_frames_u8_pack per pathway (pad channels
+ * zero); the resized uint8 frames stay in LDS.  bounds_* / kk_* are the DEVICE copies of the
+ * vs_resize_coeffs tables of each axis (unused, may be NULL, for an axis whose size does not change);
+ * cpad_* is 4 (stem kernels) or 8; mean3 / std3 are HOST pointers.  One block per (frame, band of output
+ * rows): vs_ingest_plan (host only, no launch) gives the band height, the rows of its LDS tile and the
+ * block's LDS bytes for a budget -- the largest band of at most 32 rows that fits; vs_ingest_u8 plans
+ * with 64 KiB. */
+int vs_ingest_plan(int H0, int Ho, int Wo, int lds_budget, int* band_rows, int* tile_rows, int* lds_bytes);
+int vs_ingest_u8(const uint8_t* src, void* y_fast, void* y_slow, const int* t_index_slow, int N, int T,
+                 int Tslow, int H0, int W0, int Ho, int Wo, const int32_t* bounds_h, const int32_t* kk_h,
+                 int ksize_h, const int32_t* bounds_v, const int32_t* kk_v, int ksize_v, int cpad_fast,
+                 int cpad_slow, const float* mean3, const float* std3, int reverse_channels, void* stream);
 
 /* vs_gemm_nt_f32 with a split-K workspace: GEMMs of more than 64 rows with few 64x64 output tiles (a
  * 600-token batch against a 1024-wide layer) are cut into K slices whose partial tiles are added in slice

@@ -20,7 +20,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .trunk import VideoTrunk
+from .trunk import RawFrames, VideoTrunk
 from .transformer_code import Transformer as TxCodeEnc, LinearFn
 from .hf_gpt2_fseq import (GPT2_DIMS, GPT2LMHeadModelHip, HuggingFaceGPT2Decoder, _GPT2TrainFn,
                            lm_loss as gpt2_lm_loss)
@@ -174,9 +174,10 @@ class SFBase(nn.Module):
         """The trunk's input list, events folded into the batch axis: [slow, fast], [fast], or one uint8 tensor."""
         if "frms_ev_raw_u8" in inp:
             # decoded frames at their source size [B, E, T, H0, W0, 3]: the loader's
-            # `img.resize((224, 224))` (dat_loader.py:188, PIL bicubic) runs on the GPU, bit-exact
+            # `img.resize((224, 224))` (dat_loader.py:188, PIL bicubic) runs on the GPU, bit-exact -- in eval mode
+            # fused with the normalise / pack of both pathways (one launch, `trunk.RawFrames`)
             side = int(self.sf_cfg.DATA.TRAIN_CROP_SIZE)
-            return [combine_first_ax(ops.resize_bicubic_u8(inp["frms_ev_raw_u8"], side, side))]
+            return [RawFrames(combine_first_ax(inp["frms_ev_raw_u8"]), (side, side))]
         if "frms_ev_fast_u8" in inp:
             # optional fast path beside the reference contract: the loader's uint8 RGB frames
             # [B, E, T, H, W, 3]; normalisation and the slow-pathway gather happen on the GPU

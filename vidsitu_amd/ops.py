@@ -1257,6 +1257,52 @@ def resize_bicubic_u8(frames, out_h=224, out_w=224):
     return dst
 
 
+INGEST_LDS_BUDGET = 64 * 1024
+
+
+def ingest_plan(h0, out_h, out_w, lds_budget=INGEST_LDS_BUDGET):
+    """Band planner of the fused ingest kernel (vs_ingest_plan, host only): -> (output rows per block, rows
+    of its LDS tile, LDS bytes per block) -- the largest band of at most 32 output rows whose tile of
+    horizontally resized source rows, vertical weights and normalisation table fit `lds_budget` bytes."""
+    band, rows, lds = C.c_int(0), C.c_int(0), C.c_int(0)
+    _lib.check(_lib.load().vs_ingest_plan(int(h0), int(out_h), int(out_w), int(lds_budget), C.byref(band),
+                                          C.byref(rows), C.byref(lds)), "vs_ingest_plan")
+    return band.value, rows.value, lds.value
+
+
+def ingest_u8(frames, out_h, out_w, cpad_fast, t_index=None, cpad_slow=None, mean=(0.45, 0.45, 0.45),
+              std=(0.225, 0.225, 0.225), reverse=False, out=None):
+    """Decoded frames uint8 [N, T, H0, W0, 3] -> (fast, slow): the normalised bf16 stem inputs
+    [N, cpad_fast, T, out_h, out_w] and, with `t_index` (int32 device tensor, the slow pathway's frames),
+    [N, cpad_slow, len(t_index), out_h, out_w] (else None), channels-last memory, in ONE launch: the bits of
+    `resize_bicubic_u8` followed by `frames_u8_pack` per pathway, without the uint8 intermediate.
+    `out=(fast, slow)`: write into these activations (`new_act` layout) instead of new ones."""
+    if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3:
+        raise _lib.VsError("ingest_u8 expects uint8 [N, T, H0, W0, 3]")
+    frames = frames.contiguous()
+    n, t, h0, w0, _ = frames.shape
+    dev = frames.device
+    bh, kh, _ = resize_tables(w0, out_w, dev) if w0 != out_w else (None, None, None)
+    bv, kv, _ = resize_tables(h0, out_h, dev) if h0 != out_h else (None, None, None)
+    ts = 0 if t_index is None else int(t_index.numel())
+    if out is None:
+        y_fast = new_act(n, cpad_fast, t, out_h, out_w, dev)
+        y_slow = new_act(n, cpad_slow, ts, out_h, out_w, dev) if ts else None
+    else:
+        y_fast, y_slow = out[0], (out[1] if ts else None)
+        for y, shp in ((y_fast, (n, cpad_fast, t, out_h, out_w)), (y_slow, (n, cpad_slow, ts, out_h, out_w))):
+            if y is not None and (tuple(y.shape) != shp or y.dtype != BF16 or not y.is_cuda
+                                  or not y.permute(0, 2, 3, 4, 1).is_contiguous()):
+                raise _lib.VsError(f"ingest_u8: output of shape {tuple(y.shape)}, expected a dense {shp}")
+    m3 = (C.c_float * 3)(*[float(a) for a in mean])
+    s3 = (C.c_float * 3)(*[float(a) for a in std])
+    _lib.call("vs_ingest_u8", _ptr(frames), _ptr(y_fast), _ptr(y_slow), _ptr(t_index) if ts else None, n, t, ts,
+              h0, w0, out_h, out_w, _ptr(bh), _ptr(kh), 0 if kh is None else kh.shape[1], _ptr(bv), _ptr(kv),
+              0 if kv is None else kv.shape[1], cpad_fast, cpad_slow if ts else 0, C.cast(m3, C.c_void_p),
+              C.cast(s3, C.c_void_p), int(reverse), _stream())
+    return y_fast, y_slow
+
+
 def _pad16(n):
     return (n + 15) // 16 * 16
 

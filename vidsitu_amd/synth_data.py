@@ -87,26 +87,28 @@ def synth_u8_batch(cfg, comm, bs, n_ev=5, seed=1234, device="cpu", crop=None):
     }
 
 
-def synth_video_u8_batch(cfg, comm, bs, n_ev=5, seed=1234, device="cpu", crop=None):
+def synth_video_u8_batch(cfg, comm, bs, n_ev=5, seed=1234, device="cpu", crop=None, hw=None):
     """uint8 frames with the statistics of decoded video rather than of noise (the calibration-robustness test and
     `feat_extractor`'s stand-in dataset): a spatially and temporally low-pass colour field (coarse noise, trilinear
     upsampling: neighbouring pixels and frames are strongly correlated), per-VIDEO brightness and contrast (events of a
-    video share them, videos differ), a little sensor noise, clipped to 0..255.  Same dict as `synth_u8_batch`."""
+    video share them, videos differ), a little sensor noise, clipped to 0..255.  Same dict as `synth_u8_batch`.
+    `hw=(H, W)`: frames of that (not necessarily square) size instead of `crop` x `crop` -- decoded video at its source
+    size, what `frms_ev_raw_u8` carries."""
     import torch.nn.functional as F
 
     sf = cfg.sf_mdl
     g = torch.Generator(device="cpu").manual_seed(seed)
     t = sf.DATA.NUM_FRAMES
-    hw = crop or sf.DATA.TRAIN_CROP_SIZE
-    coarse = torch.randn(bs * n_ev, 3, max(2, t // 8), max(2, hw // 16), max(2, hw // 16), generator=g)
-    mid = torch.randn(bs * n_ev, 3, max(2, t // 4), max(2, hw // 4), max(2, hw // 4), generator=g)
-    field = (F.interpolate(coarse, size=(t, hw, hw), mode="trilinear", align_corners=False)
-             + 0.35 * F.interpolate(mid, size=(t, hw, hw), mode="trilinear", align_corners=False))
-    field = (field / field.std()).view(bs, n_ev, 3, t, hw, hw)                # unit spread: `contrast` is in grey levels
+    fh, fw = hw if hw is not None else (crop or sf.DATA.TRAIN_CROP_SIZE,) * 2
+    coarse = torch.randn(bs * n_ev, 3, max(2, t // 8), max(2, fh // 16), max(2, fw // 16), generator=g)
+    mid = torch.randn(bs * n_ev, 3, max(2, t // 4), max(2, fh // 4), max(2, fw // 4), generator=g)
+    field = (F.interpolate(coarse, size=(t, fh, fw), mode="trilinear", align_corners=False)
+             + 0.35 * F.interpolate(mid, size=(t, fh, fw), mode="trilinear", align_corners=False))
+    field = (field / field.std()).view(bs, n_ev, 3, t, fh, fw)                # unit spread: `contrast` is in grey levels
     bright = 60.0 + 120.0 * torch.rand(bs, 1, 1, 1, 1, 1, generator=g)        # per video
     tint = 12.0 * torch.randn(bs, 1, 3, 1, 1, 1, generator=g)                 # per video and colour channel
     contrast = 25.0 + 55.0 * torch.rand(bs, 1, 1, 1, 1, 1, generator=g)       # per video
-    noise = 3.0 * torch.randn(bs, n_ev, 3, t, hw, hw, generator=g)
+    noise = 3.0 * torch.randn(bs, n_ev, 3, t, fh, fw, generator=g)
     img = (bright + tint + contrast * field + noise).round().clamp_(0, 255).to(torch.uint8)
     fr = img.permute(0, 1, 3, 4, 5, 2).contiguous()                           # [B, E, T, H, W, 3]
     return {

@@ -1018,6 +1018,26 @@ def ops_ensure_act(t):
     return t
 
 
+class RawFrames:
+    """Decoded uint8 frames [N, T, H0, W0, 3] at their source size, handed to the trunk in place of its input list's
+    one uint8 tensor, with the size the stems take.  An eval-mode pass turns them into both pathways' packed stem
+    inputs in ONE launch (`ops.ingest_u8`, before the pathway fork of `_run`); a training-mode pass resizes first
+    (`resized()`) and keeps the per-pathway pack launches on the pathways' own streams.  `shape` / `dtype` are those
+    of the resized frames, so shape arithmetic on the input list needs no special case."""
+
+    dtype = torch.uint8
+
+    def __init__(self, frames, out_hw):
+        if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3:
+            raise ops._lib.VsError("RawFrames expects uint8 [N, T, H0, W0, 3]")
+        self.frames, self.out_hw = frames, (int(out_hw[0]), int(out_hw[1]))
+        self.shape = torch.Size((frames.shape[0], frames.shape[1], self.out_hw[0], self.out_hw[1], 3))
+        self.device, self.is_cuda = frames.device, frames.is_cuda
+
+    def resized(self):
+        return ops.resize_bicubic_u8(self.frames, *self.out_hw)
+
+
 class _Fork:
     """Fork / join of the two pathways onto two HIP streams.  Between two lateral connections the
     slow and the fast pathway are independent chains; the fast one (1/8 of the channels) is made of
@@ -1140,6 +1160,10 @@ class VideoTrunk(nn.Module):
         self._weights_version = None
         self._folds_version = None
         self._stats_epoch = 0  # bumped whenever a train-mode pass rewrites running stats
+        # bumped whenever what an eval forward reads besides its input can change: a re-fold of the BNs, a rebuild of
+        # the bf16 weight copies, calibrate / reset_weight_rounding.  A captured eval graph is valid for ONE value
+        # (eval_graph.EvalGraph records it at capture and refuses to replay under another)
+        self.eval_version = 0
         self.debug_taps = None  # set to a dict to record the activations after every stage
         self._wgrad_batch, self._reduce_pending = None, False
         self.num_classes = int(getattr(cfg.MODEL, "NUM_CLASSES", 400))
@@ -1164,6 +1188,7 @@ class VideoTrunk(nn.Module):
         for c in self._convs():
             c.refresh()
         self._weights_version = self._version_key()
+        self.eval_version += 1
 
     def _version_key(self):
         return tuple((c.weight._version, c.weight.data_ptr()) for c in self._convs())
@@ -1176,6 +1201,14 @@ class VideoTrunk(nn.Module):
             (b.weight._version, b.bias._version, b.running_mean._version, b.running_var._version,
              b.weight.data_ptr()) for b in self._bns())
 
+    def eval_state_version(self):
+        """What a captured eval forward is valid for: (`eval_version`, nothing pending).  A train-mode pass, an optimizer
+        step or a `load_state_dict` does not re-fold or rebuild anything by itself -- the next eager eval forward does,
+        lazily -- so the counter alone would let a graph replay stale folds until then; the second member is False
+        from the moment the parameters / running statistics differ from what the folds and weight copies were made of."""
+        fresh = self._weights_version == self._version_key() and self._folds_version == self._fold_key()
+        return (self.eval_version, fresh)
+
     def _ensure_folds(self):
         """Eval mode: BN folds to a per-channel (scale, shift) applied in the conv epilogue;
         recomputed only when parameters / running statistics changed."""
@@ -1187,6 +1220,7 @@ class VideoTrunk(nn.Module):
                 b.fold_raw = (sc, sh)
                 b.fold = (sc, sh) if b.wround_bias is None else (sc, sh - sc * b.wround_bias)
             self._folds_version = key
+            self.eval_version += 1
 
     def calibrate_weight_rounding(self, x):
         """Eval-mode bias correction for the bf16 rounding of the convolution weights (north_star: "logits within 1e-3
@@ -1215,6 +1249,7 @@ class VideoTrunk(nn.Module):
             ResBlock.fuse_bc, _Unit.split_weights = fb, sw
         self._wround_key = self._version_key()
         self._folds_version = None  # re-fold (the corrected folds of the pass are what a re-fold produces)
+        self.eval_version += 1
         return n
 
     def reset_weight_rounding(self):
@@ -1222,6 +1257,7 @@ class VideoTrunk(nn.Module):
             b.wround_bias = None
         self._wround_key = None
         self._folds_version = None
+        self.eval_version += 1
 
     # ---- forward ------------------------------------------------------------------
     def forward_features(self, x):
@@ -1233,6 +1269,8 @@ class VideoTrunk(nn.Module):
             self.refresh_weights()
             if getattr(self, "_wround_key", None) is not None and self._wround_key != self._weights_version:
                 self.reset_weight_rounding()  # measured with other weights
+        if self.training and isinstance(x[0], RawFrames):
+            x = [x[0].resized()]
         if self.training and torch.is_grad_enabled():
             tick = torch.zeros(1, device=x[0].device, requires_grad=True)
             return list(_TrunkFn.apply(self, tick, *x))
@@ -1275,8 +1313,25 @@ class VideoTrunk(nn.Module):
             ho0, wo0 = (sh0[3] + 6 - 7) // 2 + 1, (sh0[4] + 6 - 7) // 2 + 1
             s1_buf = ops.new_act(sh0[0], st0.conv.cout + self.s1_fuse.conv_f2s.cout, sh0[2],
                                  (ho0 + 2 - 3) // 2 + 1, (wo0 + 2 - 3) // 2 + 1, dev)
+        if isinstance(inputs[0], RawFrames):
+            # decoded frames at source size (eval): resize + normalise + pack of BOTH pathways in one launch.  It writes
+            # both pathways' inputs, so it runs -- and its buffers are allocated -- on the caller's stream BEFORE the
+            # fork; the side stream is ordered behind it by the fork, and the buffers live until this pass has joined
+            # for the last time (`xin`).  (The hazard above is the stem's weight gradient reading a packed input after
+            # the forward's join; an eval pass saves nothing.)
+            assert not train
+            n, t, h, w, _ = inputs[0].shape
+            stems = [getattr(self.s1, f"pathway{p}_stem").conv.is_stem for p in range(P)]
+            tidx = self._slow_index(t, dev) if self.multi else None
+            y_fast, y_slow = ops.ingest_u8(inputs[0].frames, h, w, 4 if stems[-1] else 8, tidx, 4 if stems[0] else 8,
+                                           self.data_mean, self.data_std, self.data_reverse)
+            for p, y in enumerate([y_slow, y_fast] if self.multi else [y_fast]):
+                xin.append((y, None) if stems[p] else y)
+                shapes.append((n, 3, y.shape[2], h, w))
         par.fork()
-        if inputs[0].dtype == torch.uint8:
+        if isinstance(inputs[0], RawFrames):
+            pass
+        elif inputs[0].dtype == torch.uint8:
             # uint8 frames [N, T, H, W, 3] (what the loader's PIL step produces): normalise, pack and
             # gather the slow pathway's frames on the GPU (vs_frames_u8_pack), one launch per pathway
             fr = inputs[0]

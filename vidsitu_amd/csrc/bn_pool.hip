@@ -1821,7 +1821,7 @@ __global__ void maxpool_hw2_fwd_kernel(const uint16_t* x, uint16_t* y, uint8_t* 
       unpack8_bf16(*(const uint4*)(x + pos * C + c8 * 8), v);
 #pragma unroll
       for (int e = 0; e < 8; ++e)
-        if (q == 0 || v[e] > best[e]) {  // first maximum wins (torch's tie rule)
+        if (q == 0 || v[e] > best[e] || (v[e] != v[e] && best[e] == best[e])) {  // first maximum wins, NaN propagates (torch)
           best[e] = v[e];
           bi[e] = (uint8_t)q;
         }

@@ -597,6 +597,18 @@ int vs_beam_topk(const float* logits, const float* cum, const int64_t* forced, f
                  int64_t* out_idx, int rows, int V, int k, int pad, int eos, int unk,
                  float unk_penalty, float temperature, int flags, void* workspace, size_t ws_bytes,
                  void* stream);
+/* vs_beam_topk with n-gram blocking (no_repeat_ngram_size = ngram) applied inside the scoring kernels:
+ * tokens[rows][tok_ld] (int64) is every row's history, of which positions 0..step are read; each
+ * token that followed an earlier occurrence of the row's last ngram-1 tokens scores -inf (after the
+ * log-softmax, no renormalisation; nothing is banned while step + 2 - ngram < 0; ngram == 1 bans every
+ * token of the history).  Token ids outside [0, V) are ignored.  Same launches and workspace as
+ * vs_beam_topk; ngram == 0 is vs_beam_topk.  Without a workspace (or V <= 2048) the ban bitmap of
+ * V / 8 bytes lives in LDS and must not exceed 32 KiB. */
+int vs_beam_topk_ngram(const float* logits, const float* cum, const int64_t* forced,
+                       const int64_t* tokens, int tok_ld, int step, int ngram, float* out_val,
+                       int64_t* out_idx, int rows, int V, int k, int pad, int eos, int unk,
+                       float unk_penalty, float temperature, int flags, void* workspace,
+                       size_t ws_bytes, void* stream);
 /* Mean token cross entropy with ignore_index (Simple_TxDec.forward, mdl_sf_base.py:660-664):
  * nll_rows[rows] scratch, loss_out[2] = {mean nll over counted rows, count}; ld = row pitch. */
 int vs_xent_ignore(const float* logits, const int64_t* labels, float* nll_rows, float* loss_out,

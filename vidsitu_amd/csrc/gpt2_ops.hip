@@ -537,6 +537,9 @@ extern "C" int vs_kv_gather(const float* src, float* dst, const int64_t* index, 
 // (step < min_len);  forced[r] >= 0: only that token keeps its score (prefix forcing);
 // then + cum[r] and the k best (value, token) of the row, descending, ties -> lowest token.
 // One block per row; every thread keeps its own top-k over a strided slice, merged through LDS.
+// BAN (vs_beam_topk_ngram): n-gram blocking (seq_gen.py:374-375, 718-772) -- every token that followed
+// an earlier occurrence of the row's last n-1 tokens gets lp = -inf, after the log-softmax and without
+// renormalisation.  It only writes -inf, so it commutes with the rules above.
 // ----------------------------------------------------------------------------
 #define BT_MAXK 32
 
@@ -544,16 +547,43 @@ __device__ __forceinline__ bool bt_better(float v, int i, float w, int j) {
   return v > w || (v == w && i < j);
 }
 
+// Sets bit t - base of bm for every banned token t in [base, base + nbits) of one row: threads stride
+// over the start positions i of the earlier n-1-grams, n-1 compares each against the suffix
+// row[step+2-n .. step]; the follower row[i+n-1] lies at or before `step` -- nothing after it is read
+// (the tail of the search's token buffer is uninitialised).  step + 2 - n < 0: no start position,
+// nothing banned (:756).  The caller zeroes bm and syncs before, and syncs after; a set has no order.
+__device__ __forceinline__ void bt_mark_banned(const int64_t* row, int step, int n, int base, int nbits,
+                                               int V, unsigned* bm, int tid) {
+  const int s0 = step + 2 - n;
+  for (int i = tid; i < s0; i += 256) {
+    bool eq = true;
+    for (int j = 0; j < n - 1 && eq; ++j) eq = row[i + j] == row[s0 + j];
+    if (!eq) continue;
+    const long long t = row[i + n - 1];
+    if (t < base || t >= V || t - base >= nbits) continue;
+    const int o = (int)(t - base);
+    atomicOr(&bm[o >> 5], 1u << (o & 31));
+  }
+}
+
+template <bool BAN>
 __global__ __launch_bounds__(256) void beam_topk_kernel(const float* logits, const float* cum,
-                                                        const int64_t* forced, float* out_val,
+                                                        const int64_t* forced, const int64_t* tokens,
+                                                        int tok_ld, int step, int ngram, float* out_val,
                                                         int64_t* out_idx, int V, int k, int pad,
                                                         int eos, int unk, float unk_penalty,
                                                         float inv_temp, int flags) {
+  extern __shared__ unsigned bt_bm[];  // BAN: (V + 31) / 32 words, one bit per token of the row
   __shared__ float red[256];
   __shared__ float cv[256 * 4];
   __shared__ int ci[256 * 4];
   const int r = blockIdx.x, tid = threadIdx.x;
   const float* x = logits + (long long)r * V;
+  if (BAN) {  // the syncs of the reductions below order these stores before score() reads them
+    for (int w = tid; w < (V + 31) / 32; w += 256) bt_bm[w] = 0u;
+    __syncthreads();
+    bt_mark_banned(tokens + (long long)r * tok_ld, step, ngram, 0, V, V, bt_bm, tid);
+  }
   float mx = -INFINITY;
   for (int j = tid; j < V; j += 256) mx = fmaxf(mx, x[j] * inv_temp);
   red[tid] = mx;
@@ -588,6 +618,7 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* logits, con
     } else if ((flags & 2) && j == eos) {
       lp = -INFINITY;
     }
+    if (BAN && ((bt_bm[j >> 5] >> (j & 31)) & 1u)) lp = -INFINITY;
     return lp + add;
   };
   // k rounds of a block-wide argmax; each round every thread rescans its slice for its best
@@ -692,13 +723,22 @@ __device__ __forceinline__ void bt_block_argbest(float& bv, int& bi, float* cv, 
     }
 }
 
+template <bool BAN>
 __global__ __launch_bounds__(256) void beam_topk_part_kernel(
-    const float* logits, const float2* part, const float* cum, const int64_t* forced, float* cand_val,
-    int* cand_idx, int V, int k, int pad, int eos, int unk, float unk_penalty, float inv_temp, int flags) {
+    const float* logits, const float2* part, const float* cum, const int64_t* forced,
+    const int64_t* tokens, int tok_ld, int step, int ngram, float* cand_val, int* cand_idx, int V, int k,
+    int pad, int eos, int unk, float unk_penalty, float inv_temp, int flags) {
   __shared__ float cv[4];
   __shared__ int ci[4];
+  __shared__ unsigned bm[BAN ? BT_SLICE / 32 : 1];  // BAN: one bit per token of this slice
   const int sl = blockIdx.x, r = blockIdx.y, tid = threadIdx.x, S = gridDim.x;
   const float* x = logits + (long long)r * V;
+  if (BAN) {
+    if (tid < BT_SLICE / 32) bm[tid] = 0u;
+    __syncthreads();
+    bt_mark_banned(tokens + (long long)r * tok_ld, step, ngram, sl * BT_SLICE, BT_SLICE, V, bm, tid);
+    __syncthreads();
+  }
   float M = -INFINITY;
   for (int q = 0; q < S; ++q) M = fmaxf(M, part[(long long)r * S + q].x);
   float sum = 0.f;
@@ -726,6 +766,7 @@ __global__ __launch_bounds__(256) void beam_topk_part_kernel(
     } else if ((flags & 2) && j == eos) {
       lp = -INFINITY;
     }
+    if (BAN && ((bm[(e * 256 + tid) >> 5] >> (tid & 31)) & 1u)) lp = -INFINITY;
     v[e] = ok ? lp + add : -INFINITY;
     idx[e] = ok ? j : 0x7fffffff;
   }
@@ -791,10 +832,37 @@ __global__ __launch_bounds__(256) void beam_topk_merge_kernel(const float* cand_
 }
 
 static inline int bt_slices(int V) { return (V + BT_SLICE - 1) / BT_SLICE; }
+static inline size_t bt_bitmap_bytes(int V) { return (((size_t)V + 31) / 32) * 4; }  // one-block ban bitmap
 
 extern "C" size_t vs_beam_topk_workspace_bytes(int rows, int V, int k) {
   const size_t S = (size_t)bt_slices(V);
   return (size_t)rows * S * 8 + (size_t)rows * S * (size_t)k * 8 + 256;
+}
+
+// The launches of one scoring step, sliced (workspace: partials, then slices x k candidates per row) or
+// one block per row.  BAN: with the n-gram ban (tokens, tok_ld, step, ngram), else those are unused.
+template <bool BAN>
+static void bt_launch(bool sliced, const float* logits, const float* cum, const int64_t* forced,
+                      const int64_t* tokens, int tok_ld, int step, int ngram, float* out_val,
+                      int64_t* out_idx, int rows, int V, int k, int pad, int eos, int unk, float unk_penalty,
+                      float temperature, int flags, void* workspace, hipStream_t stream) {
+  const int S = bt_slices(V);
+  if (sliced) {
+    float2* part = (float2*)workspace;
+    float* cval = (float*)((char*)workspace + (((size_t)rows * S * 8 + 127) & ~(size_t)127));
+    int* cidx = (int*)(cval + (size_t)rows * S * k);
+    hipLaunchKernelGGL(beam_lse_part_kernel, dim3(S, rows), dim3(256), 0, stream, logits, part, V,
+                       1.0f / temperature);
+    hipLaunchKernelGGL(beam_topk_part_kernel<BAN>, dim3(S, rows), dim3(256), 0, stream, logits, part, cum,
+                       forced, tokens, tok_ld, step, ngram, cval, cidx, V, k, pad, eos, unk, unk_penalty,
+                       1.0f / temperature, flags);
+    hipLaunchKernelGGL(beam_topk_merge_kernel, dim3(rows), dim3(256), 0, stream, cval, cidx, out_val,
+                       out_idx, S * k, k);
+    return;
+  }
+  hipLaunchKernelGGL(beam_topk_kernel<BAN>, dim3(rows), dim3(256), BAN ? bt_bitmap_bytes(V) : 0, stream,
+                     logits, cum, forced, tokens, tok_ld, step, ngram, out_val, out_idx, V, k, pad, eos, unk,
+                     unk_penalty, 1.0f / temperature, flags);
 }
 
 extern "C" int vs_beam_topk(const float* logits, const float* cum, const int64_t* forced,
@@ -804,25 +872,36 @@ extern "C" int vs_beam_topk(const float* logits, const float* cum, const int64_t
   VS_CHECK_ARG(logits && out_val && out_idx && rows > 0 && V > 1, "bad args");
   VS_CHECK_ARG(k >= 1 && k <= BT_MAXK && k < V, "k must be in [1, 32] and < V");
   VS_CHECK_ARG(temperature > 0.f, "temperature must be > 0");
-  const int S = bt_slices(V);
-  if (workspace && S >= 2 && S * k <= 1024) {
-    VS_CHECK_ARG(ws_bytes >= vs_beam_topk_workspace_bytes(rows, V, k), "workspace too small");
-    float2* part = (float2*)workspace;
-    float* cval = (float*)((char*)workspace + (((size_t)rows * S * 8 + 127) & ~(size_t)127));
-    int* cidx = (int*)(cval + (size_t)rows * S * k);
-    hipLaunchKernelGGL(beam_lse_part_kernel, dim3(S, rows), dim3(256), 0, (hipStream_t)stream, logits,
-                       part, V, 1.0f / temperature);
-    hipLaunchKernelGGL(beam_topk_part_kernel, dim3(S, rows), dim3(256), 0, (hipStream_t)stream, logits,
-                       part, cum, forced, cval, cidx, V, k, pad, eos, unk, unk_penalty,
-                       1.0f / temperature, flags);
-    hipLaunchKernelGGL(beam_topk_merge_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, cval, cidx,
-                       out_val, out_idx, S * k, k);
-    VS_CHECK_LAUNCH();
-    return VS_OK;
-  }
-  hipLaunchKernelGGL(beam_topk_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, cum,
-                     forced, out_val, out_idx, V, k, pad, eos, unk, unk_penalty, 1.0f / temperature,
-                     flags);
+  const bool sliced = workspace && bt_slices(V) >= 2 && bt_slices(V) * k <= 1024;
+  VS_CHECK_ARG(!sliced || ws_bytes >= vs_beam_topk_workspace_bytes(rows, V, k), "workspace too small");
+  bt_launch<false>(sliced, logits, cum, forced, nullptr, 0, 0, 0, out_val, out_idx, rows, V, k, pad, eos, unk,
+                   unk_penalty, temperature, flags, workspace, (hipStream_t)stream);
+  VS_CHECK_LAUNCH();
+  return VS_OK;
+}
+
+// vs_beam_topk with n-gram blocking inside the scoring kernels (same launches, same workspace):
+// tokens[rows][tok_ld] holds every row's history, positions 0..step are read.  ngram == 0 is vs_beam_topk.
+extern "C" int vs_beam_topk_ngram(const float* logits, const float* cum, const int64_t* forced,
+                                  const int64_t* tokens, int tok_ld, int step, int ngram, float* out_val,
+                                  int64_t* out_idx, int rows, int V, int k, int pad, int eos, int unk,
+                                  float unk_penalty, float temperature, int flags, void* workspace,
+                                  size_t ws_bytes, void* stream) {
+  VS_CHECK_ARG(ngram >= 0, "ngram must be >= 0");
+  if (ngram == 0)
+    return vs_beam_topk(logits, cum, forced, out_val, out_idx, rows, V, k, pad, eos, unk, unk_penalty,
+                        temperature, flags, workspace, ws_bytes, stream);
+  VS_CHECK_ARG(tokens != nullptr, "ngram > 0 needs the token history");
+  VS_CHECK_ARG(step >= 0 && step < tok_ld, "step must be in [0, tok_ld)");
+  VS_CHECK_ARG(logits && out_val && out_idx && rows > 0 && V > 1, "bad args");
+  VS_CHECK_ARG(k >= 1 && k <= BT_MAXK && k < V, "k must be in [1, 32] and < V");
+  VS_CHECK_ARG(temperature > 0.f, "temperature must be > 0");
+  const bool sliced = workspace && bt_slices(V) >= 2 && bt_slices(V) * k <= 1024;
+  VS_CHECK_ARG(!sliced || ws_bytes >= vs_beam_topk_workspace_bytes(rows, V, k), "workspace too small");
+  VS_CHECK_ARG(sliced || bt_bitmap_bytes(V) <= 32768,
+               "one block per row: the ban bitmap (V / 8 bytes) exceeds 32 KiB of LDS");
+  bt_launch<true>(sliced, logits, cum, forced, tokens, tok_ld, step, ngram, out_val, out_idx, rows, V, k, pad,
+                  eos, unk, unk_penalty, temperature, flags, workspace, (hipStream_t)stream);
   VS_CHECK_LAUNCH();
   return VS_OK;
 }

@@ -1392,7 +1392,10 @@ def kv_gather(src, dst, index, length):
 
 
 def beam_topk(logits, cum, forced, k, pad, eos, unk, unk_penalty=0.0, temperature=1.0,
-              eos_only=False, ban_eos=False):
+              eos_only=False, ban_eos=False, tokens=None, step=0, no_repeat_ngram_size=0):
+    """Per-row top-k of one search step.  no_repeat_ngram_size = n > 0 (vs_beam_topk_ngram): `tokens`
+    (int64 [rows, >= step + 1], unit inner stride) is the rows' history; tokens that followed an earlier
+    occurrence of a row's last n-1 tokens score -inf.  Only positions 0..step of `tokens` are read."""
     logits = _f32c(logits)
     rows, v = logits.shape
     val = torch.empty((rows, k), dtype=torch.float32, device=logits.device)
@@ -1400,9 +1403,19 @@ def beam_topk(logits, cum, forced, k, pad, eos, unk, unk_penalty=0.0, temperatur
     flags = (1 if eos_only else 0) | (2 if ban_eos else 0)
     ws = torch.empty(int(_lib.load().vs_beam_topk_workspace_bytes(rows, v, int(k))), dtype=torch.uint8,
                      device=logits.device)
-    _lib.call("vs_beam_topk", _ptr(logits), _ptr(cum), _ptr(forced), _ptr(val), _ptr(idx), rows, v,
-              int(k), int(pad), int(eos), int(unk), float(unk_penalty), float(temperature), flags,
-              _ptr(ws), ws.numel(), _stream())
+    if not no_repeat_ngram_size:
+        _lib.call("vs_beam_topk", _ptr(logits), _ptr(cum), _ptr(forced), _ptr(val), _ptr(idx), rows, v,
+                  int(k), int(pad), int(eos), int(unk), float(unk_penalty), float(temperature), flags,
+                  _ptr(ws), ws.numel(), _stream())
+        return val, idx
+    if (tokens is None or tokens.dtype != torch.int64 or tokens.dim() != 2 or tokens.shape[0] != rows
+            or tokens.stride(1) != 1 or tokens.device != logits.device):
+        raise _lib.VsError("beam_topk: no_repeat_ngram_size needs int64 tokens [rows, len] with unit inner stride")
+    if not 0 <= int(step) < tokens.shape[1]:
+        raise _lib.VsError("beam_topk: step must index a column of tokens")
+    _lib.call("vs_beam_topk_ngram", _ptr(logits), _ptr(cum), _ptr(forced), _ptr(tokens), int(tokens.stride(0)),
+              int(step), int(no_repeat_ngram_size), _ptr(val), _ptr(idx), rows, v, int(k), int(pad), int(eos),
+              int(unk), float(unk_penalty), float(temperature), flags, _ptr(ws), ws.numel(), _stream())
     return val, idx
 
 

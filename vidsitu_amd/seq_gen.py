@@ -11,8 +11,13 @@ best first).  Differences, all deliberate:
   every step -- the reference's incremental states are empty dicts, hence falsy
   (`seq_gen.py:197-203`, `hf_gpt2_fseq.py:179-182`); `use_kv_cache=False` reproduces that;
 * ties in the top-k (order unspecified in torch) go to the lowest flattened (beam, token) index;
-* a single model (the reference never passes more than one), no n-gram blocking, no
-  `match_source_len`, no constraints / lm_model (unused by the reference's configs: they raise).
+* `no_repeat_ngram_size` = n >= 2 (`_no_repeat_ngram`, `seq_gen.py:374-375, 718-772`) is applied inside
+  the scoring kernel (`vs_beam_topk_ngram`), which scans each row's history on the device, instead of
+  a per-step copy of the token matrix to the host and a Python dict of n-grams per row.  n = 1 is
+  refused: the reference then bans every token of the row including `tokens[:, 0]` = eos, so no
+  hypothesis can finish and its own `assert step < max_len` fires;
+* a single model (the reference never passes more than one), no `match_source_len`, no constraints /
+  lm_model (unused by the reference's configs: they raise).
 """
 import math
 import os
@@ -72,7 +77,8 @@ class _DeviceSearchSession:
 
     def __init__(self, key, dev):
         (self.bsz, self.beam, self.max_len, self.min_len, self.plen, self.V, self.pad, self.eos, self.unk,
-         self.unk_penalty, self.temperature, self.normalize, self.len_penalty, self.kv, _) = key
+         self.unk_penalty, self.temperature, self.normalize, self.len_penalty, self.kv, self.ngram,
+         _) = key
         bsz, beam, max_len = self.bsz, self.beam, self.max_len
         rows, Lt, Ls = bsz * beam, max_len + 2, max_len + 1
         self.rows, self.Lt, self.Ls = rows, Lt, Ls
@@ -134,7 +140,9 @@ class _DeviceSearchSession:
         cum = None if step == 0 else self.sc[cur][:, step - 1].contiguous()
         row_val, row_idx = ops.beam_topk(logits, cum, forced, self.k, self.pad, self.eos, self.unk,
                                          self.unk_penalty, self.temperature,
-                                         eos_only=step >= self.max_len, ban_eos=ban_eos)
+                                         eos_only=step >= self.max_len, ban_eos=ban_eos,
+                                         tokens=self.tok[cur], step=step,
+                                         no_repeat_ngram_size=self.ngram)
         anc_in, anc_out = (self.anc[cur], self.anc[1 - cur]) if self.anc is not None else (None, None)
         ops.beam_step(row_val, row_idx, self.tok[cur], self.tok[1 - cur], self.sc[cur], self.sc[1 - cur],
                       self.ignore, self.finished, self.nfin, self.remaining, self.fin_tok, self.fin_score,
@@ -207,8 +215,13 @@ class SeqGenCustom(nn.Module):
         self.normalize_scores, self.len_penalty = normalize_scores, len_penalty
         self.unk_penalty, self.temperature = unk_penalty, temperature
         assert temperature > 0, "--temperature must be greater than 0"
-        if match_source_len or no_repeat_ngram_size > 0 or search_strategy is not None or lm_model is not None:
+        if match_source_len or search_strategy is not None or lm_model is not None:
             raise NotImplementedError("option unused by the reference's configs (configs/vsitu_cfg.yml:76-85)")
+        if no_repeat_ngram_size < 0 or no_repeat_ngram_size == 1:
+            raise NotImplementedError(
+                "no_repeat_ngram_size must be 0 or >= 2: with 1 the reference bans every token of the row, "
+                "tokens[:, 0] = eos included, so no hypothesis can ever finish (seq_gen.py:739-772)")
+        self.no_repeat_ngram_size = int(no_repeat_ngram_size)
         self.use_kv_cache = use_kv_cache
         # device_search: the bookkeeping between two decoder calls runs in one kernel per step
         # (vs_beam_step) with a host sync every 8 steps only; False = the torch-op mirror of the
@@ -254,7 +267,7 @@ class SeqGenCustom(nn.Module):
         dec = self.model.single_model.decoder
         key = (bsz, self.beam_size, max_len, self.min_len, plen, self.vocab_size, self.pad, self.eos,
                self.unk, float(self.unk_penalty), float(self.temperature), bool(self.normalize_scores),
-               float(self.len_penalty), bool(self.use_kv_cache), str(dev))
+               float(self.len_penalty), bool(self.use_kv_cache), self.no_repeat_ngram_size, str(dev))
         cache = dec.__dict__.setdefault("_vs_search_sessions", {})
         ses = cache.pop(key, None)
         if ses is None:
@@ -317,7 +330,8 @@ class SeqGenCustom(nn.Module):
             cum = None if step == 0 else scores[:, step - 1].contiguous()
             row_val, row_idx = ops.beam_topk(logits, cum, forced, k, self.pad, self.eos, self.unk,
                                              self.unk_penalty, self.temperature,
-                                             eos_only=step >= max_len, ban_eos=ban_eos)
+                                             eos_only=step >= max_len, ban_eos=ban_eos, tokens=tokens,
+                                             step=step, no_repeat_ngram_size=self.no_repeat_ngram_size)
             # fairseq BeamSearch.step on the per-row lists: step 0 uses the first beam only
             rv, ri = row_val.view(bsz, beam, k), row_idx.view(bsz, beam, k)
             if step == 0:

@@ -13,6 +13,8 @@
 //   unit' = unit ^ ((row & 3) << 2) ^ (((row >> 3) & 1) << 4).
 // Split-K partials go to fp32 slabs [S][Cout][K'] and are summed in a fixed
 // order by a second kernel (bitwise reproducible; no atomics).
+// conv_wgrad_kernel stages global -> registers -> LDS (two LDS stages) with a per-tile register prefetch depth
+// (wg_depth below): the 32- and 16-row tiles keep two 64-position steps of loads in flight per block and never drain.
 #include <stdlib.h>
 
 #include "common.h"
@@ -52,9 +54,30 @@ __device__ __forceinline__ int wg_swz_chunk(int row) {
   return ((row & 3) << 1) | (((row >> 3) & 1) << 3);
 }
 
+// Register prefetch depth D of conv_wgrad_kernel: the global loads of D - 1 future 64-position steps are held in
+// registers while the current step is multiplied out of LDS (two LDS stages either way).
+//   * 128- and 64-row tiles: D = 2 -- one step in flight, the pipeline restarted at every WG_ROWTAB positions while the
+//     position table is rebuilt (the 128-row tiles run on the LDS-DMA ring by default; this loop serves forced plans
+//     and kernels of more than 31 taps).
+//   * 32- and 16-row tiles (the fast pathway's res2-res4): D = WG_NARROW_DEPTH = 3.  A step's loads are 20 VGPRs per
+//     thread and the accumulators 4-16, so two steps in flight leave two blocks per CU.  The position table is then a
+//     ring of WG_ROWTAB entries refilled in halves one half ahead, the pipeline never drains inside a block, and the
+//     first dY loads are issued before the table is built.
+// Same LDS images, same step / ks / acc[a][b] order for every D: the slabs are bit for bit the same.
+// Measured per layer (profiles/wgrad_narrow_pipeline.txt): D = 3 against D = 2 is 0-12 % faster on the 32- / 16-row
+// layers (most on those of 802 816 positions), D = 4 is no better than 3 anywhere, and the 64-row tiles LOSE up to
+// 11 % at either depth -- these launches are not a chain of memory round trips: the depth of the prefetch moves them
+// little, so what bounds a step lies elsewhere (not found yet).
+#ifndef WG_NARROW_DEPTH
+#define WG_NARROW_DEPTH 3
+#endif
+constexpr int wg_depth(int bm) { return bm <= 32 ? WG_NARROW_DEPTH : 2; }
+
 template <int BM, int BN, int WM, int WN, int MODE>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int D = wg_depth(BM), R = D - 1;  // R register sets = steps in flight
+  static_assert(D >= 2 && R * 64 < WG_ROWTAB / 2, "loads never run past the table half being rebuilt");
   constexpr int TM = BM / WM, TN = BN / WN;
   constexpr int MR = TM / 16, NR = TN / 16;
   constexpr int CM = BM / 8, CN = BN / 8;            // 16-byte chunks per row
@@ -100,7 +123,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
     dt = t2 / p.kH;
   }
 
-  u32x4 ra[IM], rb[IN];
+  u32x4 ra[R][IM], rb[R][IN];  // (indexed by unrolled constants only)
   const __amdgpu_buffer_rsrc_t xsrc =
       __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)p.x_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t dysrc =
@@ -112,15 +135,18 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
       : (unsigned)(ncol * 2);
 
   // branch-free loads: every predicate becomes an out-of-range offset (buffer_load -> zeros)
-  auto gload = [&](int pstep, int chunk0) __attribute__((always_inline)) {
+  // (u: register set.  The table is addressed as a ring of WG_ROWTAB positions counted from pbeg.)
+  auto gload_a = [&](int u, int pstep) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < IM; ++i) {
       const int r = rm + RPM * i;
       const int pp = pstep + r;
       const unsigned ok = (unsigned)(r < 64) & (unsigned)mcol_ok & (unsigned)(pp < pend);
       const unsigned off = ok ? (unsigned)pp * (unsigned)(p.dy_ld * 2) + dycol : WG_OOB;
-      ra[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(dysrc, off, 0, 0));
+      ra[u][i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(dysrc, off, 0, 0));
     }
+  };
+  auto gload_b = [&](int u, int pstep) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < IN; ++i) {
       const int r = rn + RPN * i;
@@ -130,28 +156,54 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
       if (MODE == 0) {
         off = (unsigned)pp * (unsigned)(p.x_ld * 2) + xtap;
       } else {
-        const int4 e = rowtab[(pp - chunk0) & (WG_ROWTAB - 1)];
+        const int4 e = rowtab[(pp - pbeg) & (WG_ROWTAB - 1)];
         const int ti = e.y + dt, hi = e.z + dh, wi = e.w + dw;
         ok &= (unsigned)((unsigned)ti < (unsigned)p.Ti) & (unsigned)((unsigned)hi < (unsigned)p.Hi) &
               (unsigned)((unsigned)wi < (unsigned)p.Wi);
         off = (unsigned)e.x + xtap;
       }
-      rb[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, ok ? off : WG_OOB, 0, 0));
+      rb[u][i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, ok ? off : WG_OOB, 0, 0));
     }
   };
 
-  auto sstore = [&](int buf) __attribute__((always_inline)) {
+  auto sstore = [&](int u, int buf) __attribute__((always_inline)) {
     char* A = smem + buf * STAGE;
     char* B = A + IMG;
 #pragma unroll
     for (int i = 0; i < IM; ++i) {
       const int r = rm + RPM * i;
-      if (r < 64) *(u32x4*)(A + r * 256 + ((ccm ^ wg_swz_chunk(r)) << 4)) = ra[i];
+      if (r < 64) *(u32x4*)(A + r * 256 + ((ccm ^ wg_swz_chunk(r)) << 4)) = ra[u][i];
     }
 #pragma unroll
     for (int i = 0; i < IN; ++i) {
       const int r = rn + RPN * i;
-      if (r < 64) *(u32x4*)(B + r * 256 + ((ccn ^ wg_swz_chunk(r)) << 4)) = rb[i];
+      if (r < 64) *(u32x4*)(B + r * 256 + ((ccn ^ wg_swz_chunk(r)) << 4)) = rb[u][i];
+    }
+  };
+
+  // table entries of `count` positions from pbeg + rel0 on: (byte offset of the window's corner, its t / h / w)
+  auto build_tab = [&](int rel0, int count) __attribute__((always_inline)) {
+    for (int i = tid; i < count; i += 256) {
+      const int pp = pbeg + rel0 + i;
+      int4 e = make_int4(0, -(1 << 20), -(1 << 20), -(1 << 20));
+      if (pp < pend) {
+        int wo, t1, ho, t2, to, n;
+        if (p.P < (1 << 24)) {
+          fast_divmod(pp, p.Wo, 1.0f / (float)p.Wo, t1, wo);
+          fast_divmod(t1, p.Ho, 1.0f / (float)p.Ho, t2, ho);
+          fast_divmod(t2, p.To, 1.0f / (float)p.To, n, to);
+        } else {
+          wo = pp % p.Wo; t1 = pp / p.Wo;
+          ho = t1 % p.Ho; t2 = t1 / p.Ho;
+          to = t2 % p.To; n = t2 / p.To;
+        }
+        e.y = to * p.sT - p.pT;
+        e.z = ho * p.sH - p.pH;
+        e.w = wo * p.sW - p.pW;
+        const long long pos0 = (((long long)n * p.Ti + e.y) * p.Hi + e.z) * p.Wi + e.w;
+        e.x = (int)(unsigned)(pos0 * p.x_ld * 2);  // exact modulo 2^32 whenever the tap is valid
+      }
+      rowtab[(rel0 + i) & (WG_ROWTAB - 1)] = e;
     }
   };
 
@@ -201,52 +253,75 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
     }
   };
 
-  // positions are processed in chunks of WG_ROWTAB rows; the pipeline restarts
-  // at each chunk so the row table can be rebuilt behind a barrier.
-  for (int chunk0 = pbeg; chunk0 < pend; chunk0 += WG_ROWTAB) {
-    const int cend = min(pend, chunk0 + WG_ROWTAB);
-    if (MODE == 1) {
-      __syncthreads();  // previous chunk's readers are done
-      for (int i = tid; i < WG_ROWTAB; i += 256) {
-        const int pp = chunk0 + i;
-        int4 e = make_int4(0, -(1 << 20), -(1 << 20), -(1 << 20));
-        if (pp < cend) {
-          int wo, t1, ho, t2, to, n;
-          if (p.P < (1 << 24)) {
-            fast_divmod(pp, p.Wo, 1.0f / (float)p.Wo, t1, wo);
-            fast_divmod(t1, p.Ho, 1.0f / (float)p.Ho, t2, ho);
-            fast_divmod(t2, p.To, 1.0f / (float)p.To, n, to);
-          } else {
-            wo = pp % p.Wo; t1 = pp / p.Wo;
-            ho = t1 % p.Ho; t2 = t1 / p.Ho;
-            to = t2 % p.To; n = t2 / p.To;
-          }
-          e.y = to * p.sT - p.pT;
-          e.z = ho * p.sH - p.pH;
-          e.w = wo * p.sW - p.pW;
-          const long long pos0 = (((long long)n * p.Ti + e.y) * p.Hi + e.z) * p.Wi + e.w;
-          e.x = (int)(unsigned)(pos0 * p.x_ld * 2);  // exact modulo 2^32 whenever the tap is valid
-        }
-        rowtab[i] = e;
+  if constexpr (D == 2) {
+    // positions are processed in chunks of WG_ROWTAB rows; the pipeline restarts
+    // at each chunk so the row table can be rebuilt behind a barrier.
+    for (int chunk0 = pbeg; chunk0 < pend; chunk0 += WG_ROWTAB) {
+      const int cend = min(pend, chunk0 + WG_ROWTAB);
+      if (MODE == 1) {
+        __syncthreads();  // previous chunk's readers are done
+        build_tab(chunk0 - pbeg, WG_ROWTAB);
+        __syncthreads();
       }
+      const int nsteps = (cend - chunk0 + 63) >> 6;
+      gload_a(0, chunk0);
+      gload_b(0, chunk0);
+      __syncthreads();  // all waves finished computing on both buffers (previous chunk)
+      sstore(0, 0);
+      __syncthreads();
+      for (int st = 0; st < nsteps - 1; ++st) {  // straight-line body, last step peeled
+        const int cur = st & 1;
+        gload_a(0, chunk0 + (st + 1) * 64);
+        gload_b(0, chunk0 + (st + 1) * 64);
+        __builtin_amdgcn_sched_barrier(0);  // keep the prefetch ahead of the MFMAs
+        compute(cur);
+        __builtin_amdgcn_sched_barrier(0);
+        sstore(0, cur ^ 1);
+        __syncthreads();
+      }
+      compute((nsteps - 1) & 1);
       __syncthreads();
     }
-    const int nsteps = (cend - chunk0 + 63) >> 6;
-    gload(chunk0, chunk0);
-    __syncthreads();  // all waves finished computing on both buffers (previous chunk)
-    sstore(0);
+  } else {
+    // One pipeline over the block's whole position range.  Iteration st: issue the loads of step st + R into the
+    // register set step st left (st % R), multiply step st out of LDS stage st & 1, write step st + 1 (set (st + 1) % R,
+    // loaded R - 1 iterations ago) to the other stage, barrier.  Steps past the range load zeros from out-of-range
+    // offsets (no memory traffic) and are never multiplied.
+    // Table: half h of the ring holds positions [h * HALF, (h + 1) * HALF) from pbeg; half h + 1 is rebuilt in
+    // iteration h * SPH, over half h - 1, whose last reader (the loads of step h * SPH - 1) ran R iterations and as
+    // many barriers earlier; its first readers come SPH - R iterations later.  The loads of iteration h * SPH itself
+    // read half h (R < SPH).
+    constexpr int HALF = WG_ROWTAB / 2, SPH = HALF / 64;
+    const int nsteps = (pend - pbeg + 63) >> 6;
+#pragma unroll
+    for (int u = 0; u < R; ++u) gload_a(u, pbeg + u * 64);  // dY needs no table: in flight while it is built
+    if (MODE == 1) {
+      build_tab(0, HALF);
+      __syncthreads();
+    }
+#pragma unroll
+    for (int u = 0; u < R; ++u) gload_b(u, pbeg + u * 64);
+    sstore(0, 0);
     __syncthreads();
-    for (int st = 0; st < nsteps - 1; ++st) {  // straight-line body, last step peeled
-      const int cur = st & 1;
-      gload(chunk0 + (st + 1) * 64, chunk0);
+    auto iter = [&](int u, int st) __attribute__((always_inline)) {
+      if (MODE == 1 && (st & (SPH - 1)) == 0 && pbeg + (st / SPH + 1) * HALF < pend) build_tab((st / SPH + 1) * HALF, HALF);
+      gload_a(u, pbeg + (st + R) * 64);
+      gload_b(u, pbeg + (st + R) * 64);
       __builtin_amdgcn_sched_barrier(0);  // keep the prefetch ahead of the MFMAs
-      compute(cur);
+      compute(st & 1);
       __builtin_amdgcn_sched_barrier(0);
-      sstore(cur ^ 1);
+      sstore((u + 1) % R, (st + 1) & 1);
       __syncthreads();
+    };
+    int st = 0;
+    for (; st + R < nsteps; st += R) {  // R iterations per trip: the register sets are static
+#pragma unroll
+      for (int u = 0; u < R; ++u) iter(u, st + u);
     }
-    compute((nsteps - 1) & 1);
-    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < R - 1; ++u)
+      if (st + u < nsteps - 1) iter(u, st + u);
+    if (nsteps > 0) compute((nsteps - 1) & 1);
   }
 
   // D[m][n]: row = g*4 + reg (cout), col = li (k' column)
@@ -271,7 +346,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
 // channel chunk), NS stages, NS-1 tiles in flight behind a counted vmcnt and ONE raw barrier per
 // 64-position step; (2) the position table holds (byte offset, bitmask of valid taps) per row, is
 // double buffered and rebuilt one chunk ahead, so the pipeline never drains inside a block
-// (the register-staged kernel restarts it every 1024 positions).
+// (the register-staged kernel's 128-row tiles restart it every 1024 positions).
 // ---------------------------------------------------------------------------------------------
 // ROWS (round 4): positions per ring stage.  64 = the round-1..3 ring; 32 = half stages -- the SAME 64 KiB hold four of
 // them instead of two, i.e. three 32-position steps in flight behind `vmcnt(8)` instead of one 64-position step behind

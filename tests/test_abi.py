@@ -49,3 +49,23 @@ def test_argument_validation_without_gpu():
     rc = lib.vs_conv_fwd(None, None, None, ctypes.byref(d), None, None, None, None, None, 0, None)
     assert rc == -1
     assert b"multiples of 8" in lib.vs_last_error_string()
+
+
+def test_flag_constants_follow_the_header():
+    """Every `#define VS_CONV_* (1 << n)` / `VS_WGRAD_*` of the header equals the Python constant of the same name, and
+    the two function-like macros encode what their Python namesakes do."""
+    hdr = open(os.path.join(ROOT, "include", "vidsitu_hip.h")).read()
+    bits = re.findall(r"#define (VS_(?:CONV|WGRAD)_[A-Z0-9_]+) \(1 << (\d+)\)", hdr)
+    plain = re.findall(r"#define (VS_CONV_[A-Z0-9_]+) (\d+)\b", hdr)
+    assert len(bits) >= 14 and len(plain) == 5
+    for name, n in bits:
+        assert getattr(_lib, name) == 1 << int(n), name
+    for name, v in plain:
+        assert getattr(_lib, name) == int(v), name
+    assert "#define VS_CONV_TILE(id) (((id) + 1) << 8)" in hdr
+    assert "#define VS_CONV_RING(ns) (((ns) & 7) << 16)" in hdr
+    assert [_lib.VS_CONV_TILE(i) for i in (0, 7)] == [1 << 8, 8 << 8]
+    assert [_lib.VS_CONV_RING(i) for i in (0, 1, 4, 9)] == [0, 1 << 16, 4 << 16, 1 << 16]
+    # and the header defines nothing of the kind that Python lacks under another spelling
+    assert {n for n, _ in bits} | {n for n, _ in plain} == {n for n in dir(_lib) if re.fullmatch(r"VS_(CONV|WGRAD)_[A-Z0-9_]+", n)
+                                                       and isinstance(getattr(_lib, n), int)}

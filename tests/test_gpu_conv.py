@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from gpu_utils import assert_close, rb, to_act, to_w
+from vidsitu_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
@@ -42,6 +43,32 @@ CASES = [
     ("stem_slow", 1, 8, 2, 32, 32, 64, (1, 7, 7), (1, 2, 2), (0, 3, 3)),
     ("stem_fast", 1, 8, 8, 32, 32, 8, (5, 7, 7), (1, 2, 2), (2, 3, 3)),
 ]
+
+
+@pytest.fixture
+def guarded_partials(monkeypatch):
+    """A rows query and the launch it sizes a buffer for choose the same kernel.  Every [rows, 2, C] buffer of per-block
+    partials that ops allocates from a rows query during the test (forward BN statistics, BN-backward sums of one or
+    two units, apply on load) becomes the front of a NaN-filled buffer four rows longer.  At the end every float of
+    the `rows` rows has been written and the four rows behind them are still NaN: a launch that chose another kernel
+    than the query writes more rows or fewer.  The guard rows hold an overrun of up to four rows inside the allocation and
+    show any longer one by its first four rows; they do not contain it (a 128-row tile kernel behind a query that
+    answered for 256-row tiles writes twice the rows)."""
+    from vidsitu_amd import ops
+
+    made = []
+
+    def partials(rows, c, device):
+        full = torch.full((rows + 4, 2, c), float("nan"), dtype=torch.float32, device=device)
+        made.append((full, rows))
+        return full[:rows]
+
+    monkeypatch.setattr(ops, "_partials", partials)
+    yield made
+    assert made, "the test allocated no partials"
+    for i, (full, rows) in enumerate(made):
+        assert not bool(torch.isnan(full[:rows]).any()), f"partials {i}: not every one of the {rows} rows was written"
+        assert bool(torch.isnan(full[rows:]).all()), f"partials {i}: the launch wrote past the {rows} rows of the query"
 
 
 def _mk(case, seed=0):
@@ -101,7 +128,7 @@ def test_conv_fused_epilogue_and_concat_write(dev):
 
 @pytest.mark.parametrize("case", [CASES[1], CASES[7], CASES[10], CASES[11], CASES[13], CASES[14], CASES[17],
                                   CASES[18], CASES[20], CASES[21]], ids=lambda c: c[0])
-def test_conv_bn_stat_partials(case, dev):
+def test_conv_bn_stat_partials(case, dev, guarded_partials):
     from vidsitu_amd import ops
 
     x, w, k, s, p = _mk(case, seed=5)
@@ -220,7 +247,7 @@ def test_direct_kernel_epilogue_and_residual(dev):
     assert_close(y, y_tiled.float(), 8e-3, "direct vs tiled kernel")
 
 
-def test_splitk_path_epilogue(dev):
+def test_splitk_path_epilogue(dev, guarded_partials):
     """Few-tile deep-K shapes take the split-K plan (fp32 slabs + fused reduce/epilogue kernel):
     affine + residual + ReLU + BN partials must match, and two runs must be bit-identical."""
     from vidsitu_amd import ops
@@ -492,7 +519,7 @@ BNS_CASES = [CASES[i] for i in (0, 1, 4, 5, 6, 7, 9, 10, 11, 14, 15)] + STRIDED[
 
 
 @pytest.mark.parametrize("case", BNS_CASES, ids=[c[0] for c in BNS_CASES])
-def test_dgrad_emits_the_producer_bn_backward_sums(case, dev):
+def test_dgrad_emits_the_producer_bn_backward_sums(case, dev, guarded_partials):
     """vs_conv_dgrad_bnstats: dx bitwise the plain dgrad, and the per-tile partial sums add up to what
     vs_bn_bwd_reduce (recomputed-mask mode) computes from that dx and the producer's saved conv output --
     pointwise / gathered / strided dgrads (stride classes incl. classes no tap reaches), every tile shape
@@ -689,7 +716,7 @@ _HALO_W128 = {"w128_3x3_224": (0, 224), "w128_t3_224": (0, 224), "w128_t3_128": 
               "w128_dgrad_t3": (1, 128), "w128_dgrad_3x3": (1, 128), "s5b_3x3_512_n32": (0, 224)}
 
 
-def _plan(ops, xs, ys, x_ld, y_ld, k, s, p, dgrad, flags=1 << 22):  # VS_CONV_FORCEHALO
+def _plan(ops, xs, ys, x_ld, y_ld, k, s, p, dgrad, flags=_lib.VS_CONV_FORCEHALO):
     import ctypes as C
     d = ops.make_desc(xs, x_ld, ys, y_ld, k, s, p, flags)
     out = (C.c_int * 5)()
@@ -698,7 +725,7 @@ def _plan(ops, xs, ys, x_ld, y_ld, k, s, p, dgrad, flags=1 << 22):  # VS_CONV_FO
 
 
 @pytest.mark.parametrize("case", HALO_CASES, ids=[c[0] for c in HALO_CASES])
-def test_halo_image_kernel_fwd_and_dgrad(case, dev):
+def test_halo_image_kernel_fwd_and_dgrad(case, dev, guarded_partials):
     """conv_halo.hip (unit-stride [kT,1,1] / [1,kH,kW] convs, the activation patch incl. its halo staged once
     per 64-channel chunk): forward with every epilogue (BN-stat partials, affine + ReLU, residual) and the data
     gradient (plain, + residual, + masked residual, + the producer's BN-backward sums) against torch and
@@ -791,7 +818,7 @@ SPLITK_IL_CASES = [
 
 
 @pytest.mark.parametrize("case", SPLITK_IL_CASES, ids=[c[0] for c in SPLITK_IL_CASES])
-def test_in_launch_splitk_fwd_and_dgrad(case, dev):
+def test_in_launch_splitk_fwd_and_dgrad(case, dev, guarded_partials):
     """In-launch split-K of the 128 x 128 tile kernel (S blocks per tile store their partial accumulators, the tile's
     last arriver sums them in split order and runs the fused epilogue): forward with every epilogue and the data
     gradient (plain, + residual, + masked residual, + BN-backward sums; strided: stride classes) against torch and
@@ -806,8 +833,8 @@ def test_in_launch_splitk_fwd_and_dgrad(case, dev):
     xa, wa = to_act(x, dev), to_w(wgt, dev)
     ref = F.conv3d(x, wgt, stride=s, padding=p)
     ys = tuple(ref.shape)
-    IL = 1 << 29  # VS_CONV_SPLITK_IL (+ NOHALO | NOPW | NODEEP: the tile kernel)
-    other = (1 << 21) | (1 << 23) | (1 << 27)
+    IL = _lib.VS_CONV_SPLITK_IL  # (+ NOHALO | NOPW | NODEEP: the tile kernel)
+    other = _lib.VS_CONV_NOHALO | _lib.VS_CONV_NOPW | _lib.VS_CONV_NODEEP
     pl = _plan(ops, tuple(x.shape), ys, cin, cout, k, s, p, 0, IL | other)
     assert pl[4] == 5 and pl[3] >= 2 and pl[0] == 128 and pl[1] == 128, f"forward did not take the in-launch split: {list(pl)}"
     kw = dict(halo=False, pw=False, deep=False)
@@ -891,7 +918,7 @@ DEEP_CASES = [
 
 
 @pytest.mark.parametrize("case", DEEP_CASES, ids=[c[0] for c in DEEP_CASES])
-def test_deep_pipeline_kernel_fwd_and_dgrad(case, dev):
+def test_deep_pipeline_kernel_fwd_and_dgrad(case, dev, guarded_partials):
     """conv_deep.hip (256 x 256 x 64 tile, 8 waves, sub-buffer ring 7 phases deep): forward with every epilogue
     (BN-stat partials, affine + ReLU, residual into a wider buffer) and the unit-stride data gradient (plain,
     + residual, + masked residual, + the producer's BN-backward sums in both mask forms) against torch and against
@@ -906,8 +933,8 @@ def test_deep_pipeline_kernel_fwd_and_dgrad(case, dev):
     xa, wa = to_act(x, dev), to_w(wgt, dev)
     ref = F.conv3d(x, wgt, stride=s, padding=p)
     ys = tuple(ref.shape)
-    FORCE, NO = 1 << 28, 1 << 27  # VS_CONV_FORCEDEEP / VS_CONV_NODEEP (+ NOHALO | NOPW: the comparison kernel is the tile kernel)
-    assert _plan(ops, tuple(x.shape), ys, cin, cout, k, s, p, 0, FORCE | (1 << 21) | (1 << 23))[4] == 4, "forward did not take the deep kernel"
+    FORCE = _lib.VS_CONV_FORCEDEEP | _lib.VS_CONV_NOHALO | _lib.VS_CONV_NOPW  # (the comparison kernel is the tile kernel)
+    assert _plan(ops, tuple(x.shape), ys, cin, cout, k, s, p, 0, FORCE)[4] == 4, "forward did not take the deep kernel"
     kw = dict(halo=False, pw=False)
     y, part = ops.conv_fwd(xa, wa, k, s, p, stats=True, deep="force", **kw)
     assert_close(y, ref, TOL, name + " fwd")
@@ -940,7 +967,7 @@ def test_deep_pipeline_kernel_fwd_and_dgrad(case, dev):
     wt = ops.weight_transpose(wa)
     dya = to_act(dy, dev)
     xs = tuple(x.shape)
-    assert _plan(ops, xs, ys, cin, cout, k, s, p, 1, FORCE | (1 << 21) | (1 << 23))[4] == 4, "dgrad did not take the deep kernel"
+    assert _plan(ops, xs, ys, cin, cout, k, s, p, 1, FORCE)[4] == 4, "dgrad did not take the deep kernel"
     dx = ops.conv_dgrad(dya, wt, xs, k, s, p, deep="force", **kw)
     assert_close(dx, dx_ref, TOL, name + " dgrad")
     assert_close(dx, ops.conv_dgrad(dya, wt, xs, k, s, p, deep=False, **kw).float(), 2.0 ** -7, name + " dgrad vs tile")
@@ -1057,7 +1084,7 @@ PW_CASES = [
 
 
 @pytest.mark.parametrize("case", PW_CASES, ids=[c[0] for c in PW_CASES])
-def test_persistent_pointwise_kernel_fwd_and_dgrad(case, dev):
+def test_persistent_pointwise_kernel_fwd_and_dgrad(case, dev, guarded_partials):
     """conv_pw.hip (1x1x1 convs with K <= 512: weight slice resident in LDS, activation chunks streamed through an
     LDS-DMA ring across tile boundaries): forward with every epilogue and the unit-stride data gradient with every
     epilogue, against torch and BITWISE against the implicit-GEMM kernel (VS_CONV_NOPW) -- the two kernels run the
@@ -1073,7 +1100,7 @@ def test_persistent_pointwise_kernel_fwd_and_dgrad(case, dev):
     ref = F.conv3d(x, wgt, stride=s)
     ys = tuple(ref.shape)
     bits16 = lambda a: a.view(torch.int16)
-    assert _plan(ops, tuple(x.shape), ys, cin, cout, k, s, p, 0, flags=1 << 24)[4] == 3, "forward did not take the pointwise kernel"
+    assert _plan(ops, tuple(x.shape), ys, cin, cout, k, s, p, 0, flags=_lib.VS_CONV_FORCEPW)[4] == 3, "forward did not take the pointwise kernel"
     y, part = ops.conv_fwd(xa, wa, k, s, p, stats=True, pw="force")
     assert_close(y, ref, TOL, name + " fwd")
     y0, part0 = ops.conv_fwd(xa, wa, k, s, p, stats=True, pw=False)
@@ -1109,7 +1136,7 @@ def test_persistent_pointwise_kernel_fwd_and_dgrad(case, dev):
     wt = ops.weight_transpose(wa)
     dya = to_act(dy, dev)
     if cout <= 512:
-        assert _plan(ops, tuple(x.shape), ys, cin, cout, k, s, p, 1, flags=1 << 24)[4] == (3 if cin >= 64 else 0)
+        assert _plan(ops, tuple(x.shape), ys, cin, cout, k, s, p, 1, flags=_lib.VS_CONV_FORCEPW)[4] == (3 if cin >= 64 else 0)
     dx = ops.conv_dgrad(dya, wt, tuple(x.shape), k, s, p, pw="force")
     assert_close(dx, dx_ref, TOL, name + " dgrad")
     assert torch.equal(bits16(dx), bits16(ops.conv_dgrad(dya, wt, tuple(x.shape), k, s, p, pw=False)))
@@ -1155,7 +1182,7 @@ DIRECT_BNB_CASES = [
 
 
 @pytest.mark.parametrize("case", DIRECT_BNB_CASES, ids=[c[0] for c in DIRECT_BNB_CASES])
-def test_small_channel_dgrad_emits_bn_backward_sums(case, dev):
+def test_small_channel_dgrad_emits_bn_backward_sums(case, dev, guarded_partials):
     """conv_direct_kernel<.., BNB>: the data gradient of a small-channel conv also emits the BN-backward sums of the
     unit whose complete dz it is (both mask forms) -- dx bitwise the plain launch, sums = what the separate reduce
     pass computes over the stored dx.  (Opt-in, VS_CONV_DIRECTBNB: slower in the step than the reduce pass.)"""
@@ -1203,7 +1230,7 @@ def test_small_channel_dgrad_emits_bn_backward_sums(case, dev):
                                   ("t3_256_64", 1, 256, 8, 14, 14, 64, (3, 1, 1), (1, 0, 0)),
                                   ("pw_64_16_small", 2, 64, 8, 20, 20, 16, (1, 1, 1), (0, 0, 0))],
                          ids=lambda c: c[0])
-def test_dgrad_emits_the_sums_of_two_bn_units_fed_by_one_gradient(case, dev):
+def test_dgrad_emits_the_sums_of_two_bn_units_fed_by_one_gradient(case, dev, guarded_partials):
     """`vs_dgrad_epilogue.bn_y2 ...`: the conv-a data gradient of the block BEHIND a shortcut block is the complete
     masked output gradient of that block -- of its c unit and of its shortcut unit alike.  One epilogue emits both
     units' BN-backward sums: the same sum(g), each unit's sum(g * xhat); dx and the first unit's sums bitwise the
@@ -1325,7 +1352,7 @@ AOL_CASES = [
 
 
 @pytest.mark.parametrize("case", AOL_CASES, ids=[c[0] for c in AOL_CASES])
-def test_apply_on_load_is_bitwise_the_materialised_activation(case, dev):
+def test_apply_on_load_is_bitwise_the_materialised_activation(case, dev, guarded_partials):
     """vs_conv_fwd_aol / vs_conv_wgrad_aol (the consumer convolution forms relu(y * scale + shift) on its operand
     fragments) against vs_bn_apply followed by vs_conv_fwd / vs_conv_wgrad: outputs, BN-statistic partials and the
     weight gradient bit for bit, and the weight gradient inside a (dgrad, wgrad) pair launch too."""

@@ -107,6 +107,8 @@ def test_long_case_is_one_block_over_more_than_two_table_refills(dev):
     xa, dya, _, k, s, p = _operands(LONG, dev)
     assert dya.shape[0] * dya.shape[2] * dya.shape[3] * dya.shape[4] == 2100
     for ring in (1, 2):
-        flags = (ring << 16) | ((LONG_TILE + 1) << 8) | ((LONG_SLOTS // 8) << 24)
+        # a weight gradient's descriptor shares the ring (16..18) and forced-tile (8..11) fields of the forward flags
+        # (the tile id indexes the weight gradient's own table); bits 24..31, block slots / 8, have no name in the header
+        flags = _lib.VS_CONV_RING(ring) | _lib.VS_CONV_TILE(LONG_TILE) | ((LONG_SLOTS // 8) << 24)
         d = ops.make_desc(xa.shape, ops.act_ld(xa), dya.shape, ops.act_ld(dya), k, s, p, flags)
         assert _lib.load().vs_conv_wgrad_workspace_bytes(C.byref(d)) == 0

@@ -17,6 +17,30 @@ VS_CONV_RESIDUAL = 2
 VS_CONV_RELU = 4
 VS_CONV_STATS = 8
 VS_CONV_NAIVE = 16
+VS_CONV_SPLITK = 1 << 15
+VS_CONV_NOCLASS = 1 << 19
+VS_CONV_NOHALO = 1 << 21
+VS_CONV_FORCEHALO = 1 << 22
+VS_CONV_NOPW = 1 << 23
+VS_CONV_FORCEPW = 1 << 24
+VS_CONV_DIRECTBNB = 1 << 25
+VS_CONV_BNB2 = 1 << 26
+VS_CONV_NODEEP = 1 << 27
+VS_CONV_FORCEDEEP = 1 << 28
+VS_CONV_SPLITK_IL = 1 << 29
+VS_CONV_NOSPLITK_IL = 1 << 30
+VS_WGRAD_NODEEP = 1 << 12  # keep a weight gradient off the deep-pipeline kernel
+VS_WGRAD_FORCEDEEP = 1 << 13
+
+
+def VS_CONV_TILE(tile_id):
+    """flags bits 8..11: a forced tile id (index into ops.TILE_CFGS)."""
+    return (tile_id + 1) << 8
+
+
+def VS_CONV_RING(stages):
+    """flags bits 16..18: 0 heuristic, 1 register pipeline, 2..4 LDS-DMA ring stages."""
+    return (stages & 7) << 16
 
 
 class ConvDesc(C.Structure):

@@ -383,7 +383,7 @@ static int halo_enabled() {
 // mode: kernel MODE of the launch (1 = unit-stride gather); dgrad: mirrored taps.
 bool vs_halo_plan(const ConvP& p, int mode, int dgrad, int flags, HaloGeo* out) {
   if (!halo_enabled() || mode != 1 || (flags & VS_CONV_NOHALO)) return false;
-  if (((flags >> 8) & 0xf) != 0 || (flags & (VS_CONV_NAIVE | (7 << 12) | (1 << 15)))) return false;  // forced tile / debug
+  if (((flags >> 8) & 0xf) != 0 || (flags & ((7 << 12) | (1 << 15)))) return false;  // forced tile / debug
   const int taps = p.kT * p.kH * p.kW;
   if (taps < 2 || taps > 25) return false;
   const bool temporal = p.kT > 1 && p.kH == 1 && p.kW == 1;

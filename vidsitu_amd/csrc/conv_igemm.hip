@@ -1700,8 +1700,76 @@ static bool aol_tile_ok(const ConvPlan& pl, int mode, int K) {
   return mode == 0 && !pl.direct && pl.S == 1 && pl.tile.bm == 128 && pl.tile.bn == 128 && pl.ring == 2 && K <= 512;
 }
 
-static int launch_conv(ConvP& p, int mode, int naive, int flags, void* ws, size_t ws_bytes,
-                       hipStream_t st) {
+// ---- which kernel runs a forward convolution or a data gradient: ONE decision -------------------------------------
+enum ConvKind { CONV_NAIVE, CONV_HALO, CONV_PW, CONV_DEEP, CONV_DIRECT, CONV_TILE, CONV_SPLITK, CONV_SPLITK_IL };
+
+// What a launch knows beyond its geometry and the descriptor's flags.  The launch reads it off its arguments; a query
+// states it (vs_conv_dgrad_bnstats_rows: bnb; vs_conv_aol_ok: aol; everything else: none).
+struct ConvState {
+  bool bnb;   // dgrad that emits BN-backward sums (VS_CONV_BNBWD)
+  bool bnb2;  // ... of a second unit beside the first (vs_dgrad_epilogue.bn_y2)
+  bool aol;   // forward with apply on load (vs_conv_fwd_aol)
+};
+
+// Only the geometry member that `kind` names is valid (the others are zero); read it under a test or a switch on `kind`.
+struct ConvChoice {
+  ConvKind kind;
+  HaloGeo hg;   // CONV_HALO
+  PwGeo pg;     // CONV_PW
+  DeepGeo dg;   // CONV_DEEP
+  ConvPlan pl;  // CONV_DIRECT / CONV_TILE / CONV_SPLITK / CONV_SPLITK_IL; CONV_NAIVE: the plan it displaced (reports only)
+  // Rows of the per-block partials (BN statistics, BN-backward sums) the launch writes: the grid's row tiles -- 64-row
+  // blocks of the epilogue kernel under CONV_SPLITK; before the stride classes of a strided data gradient
+  // (setup_stride_classes renumbers them).  CONV_NAIVE writes none: the displaced plan's figure.
+  int tilesM;
+  bool aol_ok;  // an apply-on-load variant of this kernel exists
+};
+
+// The tile kernel's part of the choice: small-channel kernel, tile, split-K, in-launch split-K.
+static ConvChoice choose_tile(long long M, int Ncols, int K, int taps, int flags) {
+  ConvChoice c{};
+  c.pl = plan_conv(M, Ncols, K, taps, flags);
+  c.kind = c.pl.direct ? CONV_DIRECT : (c.pl.S == 1 ? CONV_TILE : (c.pl.in_launch ? CONV_SPLITK_IL : CONV_SPLITK));
+  c.tilesM = c.pl.direct ? direct_blocks(M)
+                         : (int)(c.kind == CONV_SPLITK ? (M + 63) / 64 : (M + c.pl.tile.bm - 1) / c.pl.tile.bm);
+  return c;
+}
+
+// Halo-image kernel, then persistent pointwise kernel, then deep-pipeline kernel, then the tile kernel's plans.
+// p: the geometry as fill_fwd_params / fill_dgrad_params left it; mode: what they returned; flags: desc.flags.
+// The rule that makes the buffers sound: a buffer sized by a query is written by a launch that made THIS call with
+// the same inputs -- nothing else decides which kernel runs, and no caller re-derives a stage of it.
+static ConvChoice choose_conv(const ConvP& p, int mode, int flags, ConvState s) {
+  ConvChoice c{};
+  if (!(flags & VS_CONV_NAIVE)) {
+    if (flags & VS_CONV_BNB2) flags |= VS_CONV_NOHALO | VS_CONV_NOPW;  // two-unit sums: the tile kernel's variant only
+    if (vs_halo_plan(p, mode, p.tmul < 0, flags, &c.hg)) {  // unit-stride [kT,1,1] / [1,kH,kW]: halo-image kernel
+      c.kind = CONV_HALO;
+      c.tilesM = c.hg.tilesM;
+      return c;
+    }
+    if (vs_pw_plan(p, mode, flags, s.bnb, &c.pg)) {  // shallow-K pointwise: persistent weight-resident kernel
+      c.kind = CONV_PW;
+      c.tilesM = c.pg.tilesM;
+      c.aol_ok = vs_pw_aol_ok(c.pg, p.K, s.bnb);
+      return c;
+    }
+    // wide, deep reductions that fill the chip with 256 x 256 tiles
+    if (vs_deep_plan(p, mode, flags, s.aol, s.bnb2 || (flags & VS_CONV_BNB2), &c.dg)) {
+      c.kind = CONV_DEEP;
+      c.tilesM = c.dg.tilesM;
+      return c;
+    }
+  }
+  c = choose_tile(p.M, p.Ncols, p.K, p.kT * p.kH * p.kW, flags);
+  if (flags & VS_CONV_NAIVE)
+    c.kind = CONV_NAIVE;
+  else
+    c.aol_ok = aol_tile_ok(c.pl, mode, p.K);
+  return c;
+}
+
+static int launch_conv(ConvP& p, int mode, int flags, void* ws, size_t ws_bytes, hipStream_t st) {
   {
     // chunk-major reduction (ConvP::korder) where a tap spans at least VS_CONV_KORDER_MIN k-tiles (default 2; 0 = never)
     static const int kmin = [] { const char* e = getenv("VS_CONV_KORDER_MIN"); return e ? atoi(e) : 2; }();
@@ -1711,42 +1779,42 @@ static int launch_conv(ConvP& p, int mode, int naive, int flags, void* ws, size_
   p.splitK = 1;
   p.slab = nullptr;
   p.sk_cnt = nullptr;
-  if (naive) {
-    const long long total = (long long)p.M * p.Ncols;
-    hipLaunchKernelGGL(conv_naive_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                       p, mode == 2 ? 1 : 0);
-    VS_CHECK_LAUNCH();
-    return VS_OK;
+  const ConvChoice ch =
+      choose_conv(p, mode, flags, {(p.flags & VS_CONV_BNBWD) != 0, p.bny2 != nullptr, p.in_scale != nullptr});
+  const ConvPlan& pl = ch.pl;
+  if (p.in_scale && !ch.aol_ok) {  // apply on load: vs_conv_aol_ok told the caller which launches exist
+    vs_set_error("conv: apply on load is not built for this plan (ask vs_conv_aol_ok)");
+    return VS_ERR_UNSUPPORTED;
   }
-  {
-    HaloGeo hg;
-    if (flags & VS_CONV_BNB2) flags |= VS_CONV_NOHALO | VS_CONV_NOPW;  // two-unit sums: the tile kernel's variant only
-    if (vs_halo_plan(p, mode, p.tmul < 0, flags, &hg)) {  // unit-stride [kT,1,1] / [1,kH,kW]: halo-image kernel
-      p.tilesM = hg.tilesM;
-      p.tilesN = hg.tilesN;
-      return vs_halo_launch(p, hg, st);
+  switch (ch.kind) {
+    case CONV_NAIVE: {
+      const long long total = (long long)p.M * p.Ncols;
+      hipLaunchKernelGGL(conv_naive_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                         p, mode == 2 ? 1 : 0);
+      VS_CHECK_LAUNCH();
+      return VS_OK;
     }
-    PwGeo pg;
-    if (vs_pw_plan(p, mode, flags, &pg)) {  // shallow-K pointwise: persistent weight-resident kernel
-      p.tilesM = pg.tilesM;
-      p.tilesN = pg.nsl;
-      return vs_pw_launch(p, pg, st);
-    }
-    DeepGeo dg;
-    if (vs_deep_plan(p, mode, flags, &dg)) {  // wide, deep reductions that fill the chip with 256 x 256 tiles
-      p.tilesM = dg.tilesM;
-      p.tilesN = dg.tilesN;
-      return vs_deep_launch(p, mode, dg, st);
-    }
+    case CONV_HALO:
+      p.tilesM = ch.hg.tilesM;
+      p.tilesN = ch.hg.tilesN;
+      return vs_halo_launch(p, ch.hg, st);
+    case CONV_PW:
+      p.tilesM = ch.pg.tilesM;
+      p.tilesN = ch.pg.nsl;
+      return vs_pw_launch(p, ch.pg, st);
+    case CONV_DEEP:
+      p.tilesM = ch.dg.tilesM;
+      p.tilesN = ch.dg.tilesN;
+      return vs_deep_launch(p, mode, ch.dg, st);
+    case CONV_DIRECT:
+      return p.Ncols <= 16 ? launch_direct<1>(p, mode, st) : launch_direct<2>(p, mode, st);
+    default:
+      break;
   }
-  const ConvPlan pl = plan_conv(p.M, p.Ncols, p.K, p.kT * p.kH * p.kW, flags);
-  if (p.in_scale) {  // apply on load: vs_conv_aol_ok told the caller which launches exist
-    if (!aol_tile_ok(pl, mode, p.K)) {
-      vs_set_error("conv: apply on load is not built for this plan (ask vs_conv_aol_ok)");
-      return VS_ERR_UNSUPPORTED;
-    }
-    p.tilesM = (p.M + 127) / 128;
-    p.tilesN = (p.Ncols + 127) / 128;
+  const TileCfg c = pl.tile;
+  p.tilesM = (p.M + c.bm - 1) / c.bm;
+  p.tilesN = (p.Ncols + c.bn - 1) / c.bn;
+  if (p.in_scale) {
     static std::once_flag attr;
     std::call_once(attr, [] {
       (void)hipFuncSetAttribute((const void*)conv_igemm_aol_kernel<128, 128, 2, 2, 2>,
@@ -1757,13 +1825,8 @@ static int launch_conv(ConvP& p, int mode, int naive, int flags, void* ws, size_
     VS_CHECK_LAUNCH();
     return VS_OK;
   }
-  if (pl.direct)
-    return p.Ncols <= 16 ? launch_direct<1>(p, mode, st) : launch_direct<2>(p, mode, st);
-  const TileCfg c = pl.tile;
-  p.tilesM = (p.M + c.bm - 1) / c.bm;
-  p.tilesN = (p.Ncols + c.bn - 1) / c.bn;
   setup_stride_classes(p, c.bm, mode, flags);
-  if (pl.S > 1 && pl.in_launch) {
+  if (ch.kind == CONV_SPLITK_IL) {
     if (ws == nullptr || ws_bytes < plan_ws_bytes(pl, p.M, p.Ncols)) {
       vs_set_error("conv: in-launch split-K workspace too small (%zu < %zu)", ws_bytes, plan_ws_bytes(pl, p.M, p.Ncols));
       return VS_ERR_WORKSPACE;
@@ -1777,7 +1840,7 @@ static int launch_conv(ConvP& p, int mode, int naive, int flags, void* ws, size_
     p.slab = (float*)((char*)ws + il_counter_bytes(p.M, p.Ncols));
     return launch_cfg<128, 128, 2, 2>(p, mode, 2, st);
   }
-  if (pl.S > 1) {
+  if (ch.kind == CONV_SPLITK) {
     if (p.res_bits) {
       vs_set_error("conv: the split-K plan has no masked-residual epilogue");
       return VS_ERR_UNSUPPORTED;
@@ -1832,7 +1895,16 @@ static int check_desc(const vs_conv_desc* d) {
 
 static int fill_dgrad_params(ConvP& p, const vs_conv_desc* d);
 
-// ConvP of a forward launch (everything but the tensor pointers and byte extents); returns the kernel MODE.
+// Byte extents of the gathered tensor and of the weights for the buffer resources of a filled p; false at 2 GiB.
+static bool set_extents(ConvP& p) {
+  const long long xb = (long long)p.nclips * p.Gt * p.Gh * p.Gw * p.g_ld * 2;
+  const long long wb = (long long)p.Ncols * p.K * 2;
+  if (xb >= (1ll << 31) || wb >= (1ll << 31)) return false;
+  p.x_bytes = (unsigned)xb;
+  p.w_bytes = (unsigned)wb;
+  return true;
+}
+
 #ifdef VS_STAMP
 static unsigned long long* g_vs_stamp = nullptr;
 // diagnostic build only: every later convolution launch stamps its blocks' phases into buf[block][8] (NULL: off)
@@ -1842,22 +1914,12 @@ extern "C" int vs_stamp_attach(void* buf) {
 }
 #endif
 
+// ConvP of a forward launch (everything but the tensor pointers and byte extents) into a zeroed p (`ConvP p{}`);
+// returns the kernel MODE.
 static int fill_fwd_params(ConvP& p, const vs_conv_desc* d) {
 #ifdef VS_STAMP
   p.stamp = g_vs_stamp;
 #endif
-  p.x = p.w = nullptr;
-  p.y = nullptr;
-  p.scale = p.shift = nullptr;
-  p.res = nullptr;
-  p.stats = nullptr;
-  p.bny = nullptr;
-  p.bn_mean = p.bn_invstd = p.bn_gamma = p.bn_beta = nullptr;
-  p.bn_bits = nullptr;
-  p.bny_ld = 0;
-  p.res_bits = nullptr;
-  p.bny2 = nullptr; p.bn_mean2 = p.bn_invstd2 = nullptr; p.stats2 = nullptr; p.bny2_ld = 0;
-  p.in_scale = p.in_shift = nullptr;
   p.M = d->N * d->To * d->Ho * d->Wo;
   p.nclips = d->N;
   p.Ncols = d->Cout;
@@ -1870,95 +1932,69 @@ static int fill_fwd_params(ConvP& p, const vs_conv_desc* d) {
   p.mulT = d->sT; p.mulH = d->sH; p.mulW = d->sW;
   p.offT = -d->pT; p.offH = -d->pH; p.offW = -d->pW;
   p.tmul = 1;
-  p.shT = p.shH = p.shW = 0;
-  p.x_bytes = p.w_bytes = 0;
   p.y_ld = d->y_ld;
   p.res_ld = d->res_ld;
   p.flags = d->flags & 0x70ff;  // epilogue bits + debug ablation
-  p.tilesM = p.tilesN = 0;
-  p.ncls = p.nslots = 0;
   const bool pointwise = (d->kT * d->kH * d->kW == 1) && d->pT == 0 && d->pH == 0 && d->pW == 0;
   p.dense = (pointwise && d->sT == 1 && d->sH == 1 && d->sW == 1) ? 1 : 0;
   return pointwise ? 0 : 1;
 }
 
 extern "C" int vs_conv_stats_rows(const vs_conv_desc* d) {
-  {
-    ConvP p;
-    HaloGeo hg;
-    const int mode = fill_fwd_params(p, d);
-    if (!(d->flags & VS_CONV_NAIVE) && vs_halo_plan(p, mode, 0, d->flags, &hg)) return hg.tilesM;
-    PwGeo pg;
-    p.flags |= d->flags & VS_CONV_RESIDUAL;
-    if (vs_pw_plan(p, mode, d->flags, &pg)) return pg.tilesM;
-    DeepGeo dg;
-    if (!(d->flags & VS_CONV_NAIVE) && vs_deep_plan(p, mode, d->flags, &dg)) return dg.tilesM;
-  }
-  const long long M = (long long)d->N * d->To * d->Ho * d->Wo;
-  const ConvPlan pl = plan_conv(M, d->Cout, d->kT * d->kH * d->kW * d->Cin, d->kT * d->kH * d->kW,
-                                d->flags);
-  if (pl.direct) return direct_blocks(M);
-  if (pl.S > 1 && !pl.in_launch) return (int)((M + 63) / 64);
-  return (int)((M + pl.tile.bm - 1) / pl.tile.bm);
+  ConvP p{};
+  const int mode = fill_fwd_params(p, d);
+  return choose_conv(p, mode, d->flags, {}).tilesM;
 }
 
+// The plan of the plain launch: no BN-backward sums, no second unit, no apply on load (the descriptor carries none).
 extern "C" int vs_conv_plan(const vs_conv_desc* d, int dgrad, int* out) {
   VS_CHECK_ARG(d != nullptr && out != nullptr, "null argument");
   const int taps = d->kT * d->kH * d->kW;
-  {
-    ConvP p;
-    HaloGeo hg;
-    const int mode = dgrad ? fill_dgrad_params(p, d) : fill_fwd_params(p, d);
-    if (mode >= 0 && !(d->flags & VS_CONV_NAIVE) && vs_halo_plan(p, mode, dgrad, d->flags, &hg)) {
-      out[0] = 32 * hg.mrw;
-      out[1] = 32 * hg.nrw;
-      vs_halo_variant(hg, &out[2], &out[3]);  // weight-ring depth, unrolled taps (0 = generic)
+  ConvP p{};
+  const int mode = dgrad ? fill_dgrad_params(p, d) : fill_fwd_params(p, d);
+  // strides the data gradient refuses (not powers of two): the tile plan of the shape, as always
+  const ConvChoice c = mode >= 0 ? choose_conv(p, mode, d->flags, {})
+                                 : choose_tile((long long)d->N * d->Ti * d->Hi * d->Wi, d->Cin, taps * d->Cout, taps,
+                                               d->flags);
+  switch (c.kind) {
+    case CONV_HALO:
+      out[0] = 32 * c.hg.mrw;
+      out[1] = 32 * c.hg.nrw;
+      vs_halo_variant(c.hg, &out[2], &out[3]);  // weight-ring depth, unrolled taps (0 = generic)
       out[4] = 2;  // halo-image kernel
       return VS_OK;
-    }
-    PwGeo pg;
-    if (mode >= 0 && vs_pw_plan(p, mode, d->flags, &pg)) {
+    case CONV_PW:
       out[0] = 64;
-      out[1] = pg.bn;
-      out[2] = pg.nslot;  // activation ring slots
+      out[1] = c.pg.bn;
+      out[2] = c.pg.nslot;  // activation ring slots
       out[3] = 1;
       out[4] = 3;  // persistent pointwise kernel
       return VS_OK;
-    }
-    DeepGeo dg;
-    if (mode >= 0 && !(d->flags & VS_CONV_NAIVE) && vs_deep_plan(p, mode, d->flags, &dg)) {
+    case CONV_DEEP:
       out[0] = 256;
       out[1] = 256;
       out[2] = 8;  // sub-buffers of the ring (7 in flight)
       out[3] = 1;
       out[4] = 4;  // deep-pipeline kernel
       return VS_OK;
-    }
+    default:  // the tile kernel's plans (VS_CONV_NAIVE: the plan it displaced)
+      out[0] = c.pl.tile.bm;
+      out[1] = c.pl.tile.bn;
+      out[2] = (taps <= 31 && c.pl.tile.bn >= 32 && !c.pl.direct) ? c.pl.ring : 0;
+      out[3] = c.pl.S;
+      out[4] = c.pl.direct ? 1 : (c.pl.S > 1 && c.pl.in_launch ? 5 : 0);  // 5: the tile kernel with the in-launch split-K sum
+      return VS_OK;
   }
-  ConvPlan pl;
-  if (dgrad) {
-    const long long M = (long long)d->N * d->Ti * d->Hi * d->Wi;
-    pl = plan_conv(M, d->Cin, taps * d->Cout, taps, d->flags);
-  } else {
-    const long long M = (long long)d->N * d->To * d->Ho * d->Wo;
-    pl = plan_conv(M, d->Cout, taps * d->Cin, taps, d->flags);
-  }
-  out[0] = pl.tile.bm;
-  out[1] = pl.tile.bn;
-  out[2] = (taps <= 31 && pl.tile.bn >= 32 && !pl.direct) ? pl.ring : 0;
-  out[3] = pl.S;
-  out[4] = pl.direct ? 1 : (pl.S > 1 && pl.in_launch ? 5 : 0);  // 5: the tile kernel with the in-launch split-K sum
-  return VS_OK;
 }
 
+// The TILE plan's need, whichever earlier stage would take the launch: an upper bound.  The descriptor does not carry
+// the launch state (BN sums of two units, apply on load) that sends a convolution back to the tile kernel, so the
+// answer must cover that kernel for every descriptor; the earlier stages need no workspace.
 extern "C" size_t vs_conv_workspace_bytes(const vs_conv_desc* d, int dgrad) {
   const int taps = d->kT * d->kH * d->kW;
-  if (dgrad) {
-    const long long M = (long long)d->N * d->Ti * d->Hi * d->Wi;
-    return plan_ws_bytes(plan_conv(M, d->Cin, taps * d->Cout, taps, d->flags), M, d->Cin);
-  }
-  const long long M = (long long)d->N * d->To * d->Ho * d->Wo;
-  return plan_ws_bytes(plan_conv(M, d->Cout, taps * d->Cin, taps, d->flags), M, d->Cout);
+  const long long M = dgrad ? (long long)d->N * d->Ti * d->Hi * d->Wi : (long long)d->N * d->To * d->Ho * d->Wo;
+  const int Ncols = dgrad ? d->Cin : d->Cout, K = taps * (dgrad ? d->Cout : d->Cin);
+  return plan_ws_bytes(choose_tile(M, Ncols, K, taps, d->flags).pl, M, Ncols);
 }
 
 extern "C" int vs_conv_fwd(const void* x, const void* w, void* y, const vs_conv_desc* d,
@@ -1970,7 +2006,7 @@ extern "C" int vs_conv_fwd(const void* x, const void* w, void* y, const vs_conv_
   VS_CHECK_ARG(!(d->flags & VS_CONV_AFFINE) || (scale && shift), "AFFINE needs scale/shift");
   VS_CHECK_ARG(!(d->flags & VS_CONV_RESIDUAL) || residual, "RESIDUAL needs residual");
   VS_CHECK_ARG(!(d->flags & VS_CONV_STATS) || stats_partial, "STATS needs stats_partial");
-  ConvP p;
+  ConvP p{};
   const int mode = fill_fwd_params(p, d);
   p.x = (const uint16_t*)x;
   p.w = (const uint16_t*)w;
@@ -1979,15 +2015,8 @@ extern "C" int vs_conv_fwd(const void* x, const void* w, void* y, const vs_conv_
   p.shift = shift;
   p.res = (const uint16_t*)residual;
   p.stats = stats_partial;
-  {
-    const long long xb = (long long)d->N * d->Ti * d->Hi * d->Wi * d->x_ld * 2;
-    const long long wb = (long long)d->Cout * p.K * 2;
-    VS_CHECK_ARG(xb < (1ll << 31) && wb < (1ll << 31), "tensor larger than 2 GiB");
-    p.x_bytes = (unsigned)xb;
-    p.w_bytes = (unsigned)wb;
-  }
-  return launch_conv(p, mode, (d->flags & VS_CONV_NAIVE) != 0, d->flags, workspace, ws_bytes,
-                     (hipStream_t)stream);
+  VS_CHECK_ARG(set_extents(p), "tensor larger than 2 GiB");
+  return launch_conv(p, mode, d->flags, workspace, ws_bytes, (hipStream_t)stream);
 }
 
 // Apply on load (train, the b -> c edge of a bottleneck): which forward convolutions can take their input as the
@@ -1997,19 +2026,15 @@ extern "C" int vs_conv_fwd(const void* x, const void* w, void* y, const vs_conv_
 extern "C" int vs_conv_aol_ok(const vs_conv_desc* d) {
   if (check_desc(d) != VS_OK) return 0;
   if (d->flags & (VS_CONV_NAIVE | VS_CONV_AFFINE | VS_CONV_RESIDUAL | VS_CONV_RELU)) return 0;
-  ConvP p;
+  ConvP p{};
   const int mode = fill_fwd_params(p, d);
   if (mode != 0 || !p.dense || p.K > 512 || p.K % 8) return 0;
-  PwGeo pg;
-  if (vs_pw_plan(p, mode, d->flags, &pg)) return vs_pw_aol_ok(pg, p) ? 1 : 0;
-  // The apply-on-load launch never runs on the deep-pipeline kernel, but vs_conv_stats_rows (which sees no in_scale)
-  // would size the statistic rows for it (256-row tiles) while the 128-row tile kernel writes twice as many rows:
-  // a descriptor the deep plan accepts is refused here -- callers pass VS_CONV_NODEEP so that the rows query and the
-  // launch agree.
-  DeepGeo dg;
-  if (vs_deep_plan(p, mode, d->flags, &dg)) return 0;
-  const ConvPlan pl = plan_conv(p.M, p.Ncols, p.K, 1, d->flags);
-  return aol_tile_ok(pl, mode, p.K) ? 1 : 0;
+  // The apply-on-load launch never runs on the deep-pipeline kernel, but vs_conv_stats_rows (which knows of no apply
+  // on load) would size the statistic rows for it (256-row tiles) while the 128-row tile kernel writes twice as many:
+  // a descriptor whose plain launch lands elsewhere is refused here -- callers pass VS_CONV_NODEEP so that the rows
+  // query and the launch agree.
+  const ConvChoice c = choose_conv(p, mode, d->flags, {false, false, true});
+  return (c.aol_ok && c.kind == choose_conv(p, mode, d->flags, {}).kind) ? 1 : 0;
 }
 
 // y = conv1x1(relu(x * in_scale[c] + in_shift[c]), w) with x the producer's raw convolution output: the operand is
@@ -2022,7 +2047,7 @@ extern "C" int vs_conv_fwd_aol(const void* x, const void* w, void* y, const vs_c
   VS_CHECK_ARG(x && w && y && in_scale && in_shift, "null tensor");
   VS_CHECK_ARG(vs_conv_aol_ok(d), "apply on load is not built for this convolution: ask vs_conv_aol_ok");
   VS_CHECK_ARG(!(d->flags & VS_CONV_STATS) || stats_partial, "STATS needs stats_partial");
-  ConvP p;
+  ConvP p{};
   const int mode = fill_fwd_params(p, d);
   p.x = (const uint16_t*)x;
   p.w = (const uint16_t*)w;
@@ -2030,14 +2055,8 @@ extern "C" int vs_conv_fwd_aol(const void* x, const void* w, void* y, const vs_c
   p.stats = stats_partial;
   p.in_scale = in_scale;
   p.in_shift = in_shift;
-  {
-    const long long xb = (long long)d->N * d->Ti * d->Hi * d->Wi * d->x_ld * 2;
-    const long long wb = (long long)d->Cout * p.K * 2;
-    VS_CHECK_ARG(xb < (1ll << 31) && wb < (1ll << 31), "tensor larger than 2 GiB");
-    p.x_bytes = (unsigned)xb;
-    p.w_bytes = (unsigned)wb;
-  }
-  return launch_conv(p, mode, 0, d->flags, nullptr, 0, (hipStream_t)stream);
+  VS_CHECK_ARG(set_extents(p), "tensor larger than 2 GiB");
+  return launch_conv(p, mode, d->flags, nullptr, 0, (hipStream_t)stream);
 }
 
 // conv b -> conv c of a bottleneck in one launch (evaluation): which (descriptor of conv b, width of conv c) pairs
@@ -2066,20 +2085,14 @@ extern "C" int vs_conv_fwd_bc(const void* x, const void* w_b, const vs_conv_desc
   VS_CHECK_ARG(x && w_b && w_c && y && scale_b && shift_b && scale_c && shift_c, "null tensor");
   VS_CHECK_ARG(vs_conv_fwd_bc_fusable(d, cout_c), "not a fusable (conv b, conv c) pair: ask vs_conv_fwd_bc_fusable");
   VS_CHECK_ARG(y_ld >= cout_c && y_ld % 8 == 0 && (!residual || (res_ld >= cout_c && res_ld % 8 == 0)), "row pitch");
-  ConvP p;
+  ConvP p{};
   const int mode = fill_fwd_params(p, d);
   VS_CHECK_ARG(mode == 1, "conv b must not be pointwise");
   p.x = (const uint16_t*)x;
   p.w = (const uint16_t*)w_b;
   p.scale = scale_b;
   p.shift = shift_b;
-  {
-    const long long xb = (long long)d->N * d->Ti * d->Hi * d->Wi * d->x_ld * 2;
-    const long long wb = (long long)d->Cout * p.K * 2;
-    VS_CHECK_ARG(xb < (1ll << 31) && wb < (1ll << 31), "tensor larger than 2 GiB");
-    p.x_bytes = (unsigned)xb;
-    p.w_bytes = (unsigned)wb;
-  }
+  VS_CHECK_ARG(set_extents(p), "tensor larger than 2 GiB");
   BcP q;
   q.w2 = (const uint16_t*)w_c;
   q.w2_bytes = (unsigned)((long long)cout_c * d->Cout * 2);
@@ -2095,22 +2108,14 @@ extern "C" int vs_conv_fwd_bc(const void* x, const void* w_b, const vs_conv_desc
   return cout_c <= 32 ? launch_direct_bc<2>(p, q, (hipStream_t)stream) : launch_direct_bc<4>(p, q, (hipStream_t)stream);
 }
 
-// ConvP of a dgrad launch (everything but the tensor pointers); returns the kernel MODE or < 0.
+// ConvP of a dgrad launch (everything but the tensor pointers) into a zeroed p; returns the kernel MODE, or < 0 with p
+// untouched (strides that are not powers of two).
 static int fill_dgrad_params(ConvP& p, const vs_conv_desc* d) {
   const int shT = ilog2_exact(d->sT), shH = ilog2_exact(d->sH), shW = ilog2_exact(d->sW);
   if (shT < 0 || shH < 0 || shW < 0) return -1;
 #ifdef VS_STAMP
   p.stamp = g_vs_stamp;
 #endif
-  p.scale = p.shift = nullptr;
-  p.stats = nullptr;
-  p.bny = nullptr;
-  p.bn_mean = p.bn_invstd = p.bn_gamma = p.bn_beta = nullptr;
-  p.bn_bits = nullptr;
-  p.bny_ld = 0;
-  p.res_bits = nullptr;
-  p.bny2 = nullptr; p.bn_mean2 = p.bn_invstd2 = nullptr; p.stats2 = nullptr; p.bny2_ld = 0;
-  p.in_scale = p.in_shift = nullptr;
   p.M = d->N * d->Ti * d->Hi * d->Wi;
   p.nclips = d->N;
   p.Ncols = d->Cin;
@@ -2127,7 +2132,6 @@ static int fill_dgrad_params(ConvP& p, const vs_conv_desc* d) {
   p.y_ld = d->x_ld;
   p.res_ld = d->res_ld;
   p.flags = d->flags & (VS_CONV_NAIVE | VS_CONV_RESIDUAL);
-  p.tilesM = p.tilesN = 0;
   const bool unit_stride = d->sT == 1 && d->sH == 1 && d->sW == 1;
   const bool pointwise =
       unit_stride && (d->kT * d->kH * d->kW == 1) && d->pT == 0 && d->pH == 0 && d->pW == 0;
@@ -2146,7 +2150,7 @@ static int dgrad_impl(const void* dy, const void* wt, void* dx, const vs_conv_de
   if (rc) return rc;
   VS_CHECK_ARG(dy && wt && dx, "null tensor");
   VS_CHECK_ARG(!(d->flags & VS_CONV_RESIDUAL) || residual, "RESIDUAL needs residual");
-  ConvP p;
+  ConvP p{};
   const int mode = fill_dgrad_params(p, d);
   VS_CHECK_ARG(mode >= 0, "strides must be powers of two");
   p.x = (const uint16_t*)dy;
@@ -2155,13 +2159,7 @@ static int dgrad_impl(const void* dy, const void* wt, void* dx, const vs_conv_de
   p.res = (const uint16_t*)residual;
   VS_CHECK_ARG(!residual_bits || (residual && d->Cin % 8 == 0), "a residual mask needs a residual");
   p.res_bits = residual_bits;
-  {
-    const long long xb = (long long)d->N * d->To * d->Ho * d->Wo * d->y_ld * 2;
-    const long long wb = (long long)d->Cin * p.K * 2;
-    VS_CHECK_ARG(xb < (1ll << 31) && wb < (1ll << 31), "tensor larger than 2 GiB");
-    p.x_bytes = (unsigned)xb;
-    p.w_bytes = (unsigned)wb;
-  }
+  VS_CHECK_ARG(set_extents(p), "tensor larger than 2 GiB");
   if (stats_partial) {
     VS_CHECK_ARG(bn_y && mean && invstd && bn_y_ld >= d->Cin && bn_y_ld % 8 == 0,
                  "BN-backward sums need the unit's saved conv output and its mean / invstd");
@@ -2190,40 +2188,30 @@ static int dgrad_impl(const void* dy, const void* wt, void* dx, const vs_conv_de
       p.stats2 = stats_partial2;
     }
   }
-  return launch_conv(p, mode, (d->flags & VS_CONV_NAIVE) != 0, d->flags, workspace, ws_bytes,
-                     (hipStream_t)stream);
+  return launch_conv(p, mode, d->flags, workspace, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int vs_conv_dgrad_bnstats_rows(const vs_conv_desc* d) {
   if (d == nullptr || (d->flags & VS_CONV_NAIVE)) return 0;
-  ConvP p;
+  ConvP p{};
   const int mode = fill_dgrad_params(p, d);
   if (mode < 0) return 0;
   // a strided dgrad with a residual: tiles of stride classes no tap reaches copy the residual without
   // passing through the epilogue
   if ((d->flags & VS_CONV_RESIDUAL) && mode == 2) return 0;
-  {
-    HaloGeo hg;
-    const int pf = (d->flags & VS_CONV_BNB2) ? (d->flags | VS_CONV_NOHALO | VS_CONV_NOPW) : d->flags;
-    if (vs_halo_plan(p, mode, 1, pf, &hg)) return hg.tilesM;
-    PwGeo pg;
-    p.flags |= VS_CONV_BNBWD;
-    if (vs_pw_plan(p, mode, pf, &pg)) return pg.tilesM;
-    DeepGeo dg;
-    if (vs_deep_plan(p, mode, pf, &dg)) return dg.tilesM;
-  }
-  const ConvPlan pl = plan_conv(p.M, p.Ncols, p.K, p.kT * p.kH * p.kW, d->flags);
-  if (pl.direct) {
+  const ConvChoice c = choose_conv(p, mode, d->flags, {true, (d->flags & VS_CONV_BNB2) != 0, false});
+  if (c.kind == CONV_DIRECT) {
     // The small-channel kernel can emit them too (one partial row per block), but it is bound by instruction
     // issue, not by bandwidth: with the mask / sum arithmetic in its copy-out the step is 0.1-0.2 ms SLOWER
     // than the plain launch plus the separate (bandwidth-bound) reduce pass -- 13.05 / 13.19 vs 12.83 / 13.08 ms,
     // A/B on one box.  Opt-in: VS_CONV_DIRECTBNB in desc.flags, or VS_DIRECT_BNB=1.
     static const int on = [] { const char* e = getenv("VS_DIRECT_BNB"); return e ? atoi(e) : 0; }();
-    return (on || (d->flags & VS_CONV_DIRECTBNB)) ? direct_blocks(p.M) : 0;
+    return (on || (d->flags & VS_CONV_DIRECTBNB)) ? c.tilesM : 0;
   }
-  if ((pl.S > 1 && !pl.in_launch) || !bnb_tile(pl.tile.bm, pl.tile.bn) || p.kT * p.kH * p.kW > 31) return 0;
-  p.tilesM = (p.M + pl.tile.bm - 1) / pl.tile.bm;
-  setup_stride_classes(p, pl.tile.bm, mode, d->flags);
+  if (c.kind == CONV_HALO || c.kind == CONV_PW || c.kind == CONV_DEEP) return c.tilesM;
+  if (c.kind == CONV_SPLITK || !bnb_tile(c.pl.tile.bm, c.pl.tile.bn) || p.kT * p.kH * p.kW > 31) return 0;
+  p.tilesM = c.tilesM;
+  setup_stride_classes(p, c.pl.tile.bm, mode, d->flags);
   return p.tilesM;
 }
 

@@ -240,17 +240,17 @@ static int pw_env(const char* name, int dflt) {
   return e ? atoi(e) : dflt;
 }
 
-bool vs_pw_plan(const ConvP& p, int mode, int flags, PwGeo* out) {
+bool vs_pw_plan(const ConvP& p, int mode, int flags, bool bnb, PwGeo* out) {
   static const int on = pw_env("VS_CONV_PW", 1), f_bn = pw_env("VS_PW_BN", 0), f_ns = pw_env("VS_PW_NSLOT", 0),
                    f_occ = pw_env("VS_PW_OCC", 0);
-  if (!on || mode != 0 || (flags & VS_CONV_NOPW) || (flags & VS_CONV_NAIVE)) return false;
+  if (!on || mode != 0 || (flags & VS_CONV_NOPW)) return false;
   if (((flags >> 8) & 0xf) || ((flags >> 16) & 7) || (flags & (VS_CONV_SPLITK | (7 << 12)))) return false;  // forced plans / debug
   if (p.kT * p.kH * p.kW != 1 || p.K > 512 || p.K % 8 || p.Ncols < 64 || p.Ncols % 8 || p.M < 2048) return false;
   PwGeo g;
   g.nk = (p.K + 63) / 64;
   g.bn = (p.Ncols >= 128 && g.nk <= 2) ? 128 : 64;
   if (f_bn == 64 || (f_bn == 128 && p.Ncols >= 128 && g.nk <= 4)) g.bn = f_bn;
-  const bool has_res = (p.flags & VS_CONV_RESIDUAL) != 0, bnb = (p.flags & VS_CONV_BNBWD) != 0;
+  const bool has_res = (p.flags & VS_CONV_RESIDUAL) != 0;
   // (bf16 staging tile: row pitch bn + 8 elements, see conv_tile_epilogue)
   g.epi_bytes = has_res ? PW_BM * g.bn * 4 : (bnb ? PW_BM * (g.bn + 8) * 2 + 16384 : PW_BM * (g.bn + 8) * 2);
   // + statbuf [2][4 * WM][BN] = 4 KB for both variants (WM * BN = 128) + 1 KB: apply-on-load constants [2][128]
@@ -321,12 +321,12 @@ static int pw_launch_aol(const ConvP& p, const PwGeo& g, hipStream_t st) {
 }
 
 // apply on load is built for the 128-column variant without the BN-backward-sums epilogue (the c units' forward)
-bool vs_pw_aol_ok(const PwGeo& g, const ConvP& p) { return g.bn == 128 && !(p.flags & VS_CONV_BNBWD) && p.K <= 128; }
+bool vs_pw_aol_ok(const PwGeo& g, int K, bool bnb) { return g.bn == 128 && !bnb && K <= 128; }
 
 int vs_pw_launch(const ConvP& p, const PwGeo& g, hipStream_t st) {
   const bool bnb = (p.flags & VS_CONV_BNBWD) != 0;
   if (p.in_scale) {
-    if (!vs_pw_aol_ok(g, p)) {
+    if (!vs_pw_aol_ok(g, p.K, bnb)) {
       vs_set_error("conv_pw: apply on load is not built for this variant");
       return VS_ERR_UNSUPPORTED;
     }

@@ -513,6 +513,9 @@ struct HaloGeo {
 };
 
 
+// The three plans below are stages of choose_conv (conv_igemm.hip), their only caller: it has already turned
+// VS_CONV_NAIVE away, and it passes the launch state they depend on (bnb: the dgrad emits BN-backward sums; aol: apply
+// on load; two_units: BN-backward sums of two units) beside the geometry in p.
 // Geometry of the halo kernel for this launch (mode = kernel MODE, dgrad: mirrored taps, flags = desc.flags),
 // or false when the implicit-GEMM kernel runs it.
 bool vs_halo_plan(const ConvP& p, int mode, int dgrad, int flags, HaloGeo* out);
@@ -533,15 +536,15 @@ struct PwGeo {
   int dense;      // rows are consecutive positions of the gathered tensor
   int dbg;        // VS_PW_DBG ablations (wrong results; tools only)
 };
-bool vs_pw_plan(const ConvP& p, int mode, int flags, PwGeo* out);
+bool vs_pw_plan(const ConvP& p, int mode, int flags, bool bnb, PwGeo* out);
 int vs_pw_launch(const ConvP& p, const PwGeo& g, hipStream_t st);
-bool vs_pw_aol_ok(const PwGeo& g, const ConvP& p);
+bool vs_pw_aol_ok(const PwGeo& g, int K, bool bnb);
 
 // ---- deep-pipeline kernel (conv_deep.hip): 256 x 256 x 64 tile, 8 waves, sub-buffer ring 7 phases deep ----
 struct DeepGeo {
   int tilesM, tilesN;  // 256 x 256 tiles (tilesM = rows of the batch-statistic / BN-backward partials)
   int smem;            // dynamic LDS of the launch
 };
-bool vs_deep_plan(const ConvP& p, int mode, int flags, DeepGeo* out);
+bool vs_deep_plan(const ConvP& p, int mode, int flags, bool aol, bool two_units, DeepGeo* out);
 int vs_deep_launch(const ConvP& p, int mode, const DeepGeo& g, hipStream_t st);
 

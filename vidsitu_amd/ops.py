@@ -16,10 +16,26 @@ import torch
 from . import _lib
 from ._lib import (  # noqa: F401  (re-exported flags)
     VS_CONV_AFFINE,
+    VS_CONV_BNB2,
+    VS_CONV_DIRECTBNB,
+    VS_CONV_FORCEDEEP,
+    VS_CONV_FORCEHALO,
+    VS_CONV_FORCEPW,
     VS_CONV_NAIVE,
+    VS_CONV_NOCLASS,
+    VS_CONV_NODEEP,
+    VS_CONV_NOHALO,
+    VS_CONV_NOPW,
+    VS_CONV_NOSPLITK_IL,
     VS_CONV_RELU,
     VS_CONV_RESIDUAL,
+    VS_CONV_RING,
+    VS_CONV_SPLITK,
+    VS_CONV_SPLITK_IL,
     VS_CONV_STATS,
+    VS_CONV_TILE,
+    VS_WGRAD_FORCEDEEP,
+    VS_WGRAD_NODEEP,
     ConvDesc,
 )
 
@@ -139,9 +155,37 @@ TILE_CFGS = [(128, 128), (64, 128), (128, 64), (64, 64), (256, 32), (256, 16), (
 _tune = None
 
 
-def tile_flag(kind, M, ncols, K, k, s, force=None):
+def tile_flag(force=None):
     """flags bits 8..11: a forced tile id, or 0 = the library's own plan (pick_tile)."""
-    return (force + 1) << 8 if force is not None else 0
+    return VS_CONV_TILE(force) if force is not None else 0
+
+
+def _partials(rows, c, device):
+    """Per-block partial sums [rows, 2, c] a convolution launch writes.  `rows` is the answer of a rows query on the
+    descriptor the launch then gets: the launch makes the same kernel choice and writes exactly these rows."""
+    return torch.empty((rows, 2, c), dtype=torch.float32, device=device)
+
+
+def _choice_flags(tile, ring, halo, pw, deep, splitk_il):
+    """The kernel-choice keywords of conv_fwd / conv_dgrad as vs_conv_desc.flags bits (A/B runs, tests).  halo / pw /
+    deep: True = the library's plan, False = never that kernel, "force" = wherever the shape is eligible; splitk_il
+    (in-launch split-K): "force" / True = wherever eligible, False = never, None = the plan."""
+    flags = tile_flag(tile) | VS_CONV_RING(ring)
+    if not halo:
+        flags |= VS_CONV_NOHALO
+    elif halo == "force":
+        flags |= VS_CONV_FORCEHALO
+    if not pw:
+        flags |= VS_CONV_NOPW
+    elif pw == "force":
+        flags |= VS_CONV_FORCEPW
+    if not deep:
+        flags |= VS_CONV_NODEEP
+    elif deep == "force":
+        flags |= VS_CONV_FORCEDEEP
+    if splitk_il is not None:
+        flags |= VS_CONV_SPLITK_IL if splitk_il else VS_CONV_NOSPLITK_IL
+    return flags
 
 
 def conv_fwd(x, w, k, s, p, out=None, scale=None, shift=None, residual=None, relu=False,
@@ -169,32 +213,16 @@ def conv_fwd(x, w, k, s, p, out=None, scale=None, shift=None, residual=None, rel
         flags |= VS_CONV_STATS
     if naive:
         flags |= VS_CONV_NAIVE
-    flags |= tile_flag("f", ys[0] * ys[2] * ys[3] * ys[4], cout, x.shape[1] * k[0] * k[1] * k[2], k, s,
-                       tile)
+    flags |= _choice_flags(tile, ring, halo, pw, deep, splitk_il)
     flags |= (dbg & 7) << 12  # diagnostic ablation builds (wrong results), tools/ only
     if splitk:
-        flags |= 1 << 15  # VS_CONV_SPLITK
-    flags |= (ring & 7) << 16  # VS_CONV_RING
-    if not halo:
-        flags |= 1 << 21  # VS_CONV_NOHALO
-    elif halo == "force":
-        flags |= 1 << 22  # VS_CONV_FORCEHALO
-    if not pw:
-        flags |= 1 << 23  # VS_CONV_NOPW
-    elif pw == "force":
-        flags |= 1 << 24  # VS_CONV_FORCEPW
-    if not deep:
-        flags |= 1 << 27  # VS_CONV_NODEEP
-    elif deep == "force":
-        flags |= 1 << 28  # VS_CONV_FORCEDEEP
-    if splitk_il is not None:  # in-launch split-K: "force" / True = wherever eligible, False = never, None = the plan
-        flags |= (1 << 29) if splitk_il else (1 << 30)  # VS_CONV_SPLITK_IL / VS_CONV_NOSPLITK_IL
+        flags |= VS_CONV_SPLITK
     d = make_desc(x.shape, act_ld(x), ys, act_ld(out), k, s, p, flags,
                   act_ld(residual) if residual is not None else 0)
     partials = None
     if stats:
         rows = _lib.load().vs_conv_stats_rows(C.byref(d))
-        partials = torch.empty((rows, 2, cout), dtype=torch.float32, device=x.device)
+        partials = _partials(rows, cout, x.device)
     need = _lib.load().vs_conv_workspace_bytes(C.byref(d), 0)
     ws = _workspace(need, x.device, "splitk") if need else None
     _lib.call("vs_conv_fwd", _ptr(x), _ptr(w), _ptr(out), C.byref(d), _ptr(scale), _ptr(shift),
@@ -204,7 +232,6 @@ def conv_fwd(x, w, k, s, p, out=None, scale=None, shift=None, residual=None, rel
 
 
 _K1, _S1, _P0 = (1, 1, 1), (1, 1, 1), (0, 0, 0)
-VS_CONV_NODEEP = 1 << 27  # include/vidsitu_hip.h
 
 
 def conv_aol_ok(x, cout, stats=True):
@@ -234,7 +261,7 @@ def conv_fwd_aol(x, w, in_scale, in_shift, out=None, stats=True):
     partials = None
     if stats:
         rows = _lib.load().vs_conv_stats_rows(C.byref(d))
-        partials = torch.empty((rows, 2, cout), dtype=torch.float32, device=x.device)
+        partials = _partials(rows, cout, x.device)
     _lib.call("vs_conv_fwd_aol", _ptr(x), _ptr(w), _ptr(out), C.byref(d), _ptr(in_scale), _ptr(in_shift),
               _ptr(partials), _stream())
     return out, partials
@@ -406,30 +433,14 @@ def conv_dgrad(dy, wt, xs, k, s, p, out=None, residual=None, naive=False, tile=N
     if out is None:
         out = new_act(*xs, device=dy.device)
     flags = (VS_CONV_NAIVE if naive else 0) | (VS_CONV_RESIDUAL if residual is not None else 0)
-    flags |= tile_flag("d", xs[0] * xs[2] * xs[3] * xs[4], xs[1], dy.shape[1] * k[0] * k[1] * k[2], k, s,
-                       tile)
-    flags |= (ring & 7) << 16  # VS_CONV_RING
+    flags |= _choice_flags(tile, ring, halo, pw, deep, splitk_il)
     if noclass:
-        flags |= 1 << 19  # VS_CONV_NOCLASS
-    if not halo:
-        flags |= 1 << 21  # VS_CONV_NOHALO
-    elif halo == "force":
-        flags |= 1 << 22  # VS_CONV_FORCEHALO
-    if not pw:
-        flags |= 1 << 23  # VS_CONV_NOPW
-    elif pw == "force":
-        flags |= 1 << 24  # VS_CONV_FORCEPW
+        flags |= VS_CONV_NOCLASS
     if direct_bnb:
-        flags |= 1 << 25  # VS_CONV_DIRECTBNB
-    if not deep:
-        flags |= 1 << 27  # VS_CONV_NODEEP
-    elif deep == "force":
-        flags |= 1 << 28  # VS_CONV_FORCEDEEP
-    if splitk_il is not None:
-        flags |= (1 << 29) if splitk_il else (1 << 30)  # VS_CONV_SPLITK_IL / VS_CONV_NOSPLITK_IL
+        flags |= VS_CONV_DIRECTBNB
     two = bn_stats2 is not None and bn_stats is not None and residual is not None and tuple(s) == (1, 1, 1)
     if two:
-        flags |= 1 << 26  # VS_CONV_BNB2
+        flags |= VS_CONV_BNB2
     d = make_desc(xs, act_ld(out), dy.shape, act_ld(dy), k, s, p, flags,
                   act_ld(residual) if residual is not None else 0)
     if residual_bits is not None:
@@ -449,7 +460,7 @@ def conv_dgrad(dy, wt, xs, k, s, p, out=None, residual=None, naive=False, tile=N
         ok = (bits is not None) if residual is not None else (bits is None and gamma is not None)
         rows = _lib.load().vs_conv_dgrad_bnstats_rows(C.byref(d)) if ok else 0
         if rows > 0:
-            partial = torch.empty((rows, 2, xs[1]), dtype=torch.float32, device=dy.device)
+            partial = _partials(rows, xs[1], dy.device)
             ep.bn_y, ep.bn_y_ld = y.data_ptr(), act_ld(y)
             ep.relu_bits = bits.data_ptr() if bits is not None else None
             ep.mean, ep.invstd = mean.data_ptr(), invstd.data_ptr()
@@ -460,7 +471,7 @@ def conv_dgrad(dy, wt, xs, k, s, p, out=None, residual=None, naive=False, tile=N
             # bn_stats2 = (y2, mean2, invstd2); residual + bit-mask form, unit stride
             if two:
                 y2, mean2, invstd2 = bn_stats2
-                partial2 = torch.empty((rows, 2, xs[1]), dtype=torch.float32, device=dy.device)
+                partial2 = _partials(rows, xs[1], dy.device)
                 ep.bn_y2, ep.bn_y2_ld = y2.data_ptr(), act_ld(y2)
                 ep.mean2, ep.invstd2 = mean2.data_ptr(), invstd2.data_ptr()
                 ep.stats_partial2 = partial2.data_ptr()
@@ -474,7 +485,6 @@ def conv_dgrad(dy, wt, xs, k, s, p, out=None, residual=None, naive=False, tile=N
 
 
 _ws_cache = {}
-VS_WGRAD_NODEEP = 1 << 12  # include/vidsitu_hip.h: keep a weight gradient off the deep-pipeline kernel
 import os as _os_wi
 # VS_WHATIF (tools/whatif.sh: whole kernel families skipped to time what they cost -- GARBAGE numerics) is refused unless
 # the tools-only guard VS_WHATIF_OK=1 stands beside it: a leaked variable must not train silently on garbage.
@@ -633,9 +643,9 @@ def conv_wgrad(dy, x, k, s, p, out=None, ring=0, batch=None, tile=None, slots=0,
     # tile: index into WG_TILES, slots: block slots to fill (multiple of 8) -- tuning knobs, 0 / None = the plan
     flags = ((ring & 7) << 16) | (((tile + 1) << 8) if tile is not None else 0) | (((slots // 8) & 0xff) << 24)
     if not deep:
-        flags |= 1 << 12  # VS_WGRAD_NODEEP: not the deep-pipeline kernel (A/B, tests)
+        flags |= VS_WGRAD_NODEEP  # not the deep-pipeline kernel (A/B, tests)
     elif deep == "force":
-        flags |= 1 << 13  # VS_WGRAD_FORCEDEEP
+        flags |= VS_WGRAD_FORCEDEEP
     d = make_desc(x.shape, act_ld(x), dy.shape, act_ld(dy), k, s, p, flags)
     need = _lib.load().vs_conv_wgrad_workspace_bytes(C.byref(d))
     ws = _workspace(need, x.device, "wgrad") if need else None

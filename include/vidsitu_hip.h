@@ -648,7 +648,8 @@ int vs_xent_ignore_grad_dev(const float* logits, const int64_t* labels, const fl
 
 /* Device-side beam-search bookkeeping of one step (SeqGenCustom._generate between two decoder
  * calls, seq_gen.py:368-520, and finalize_hypos :579-697), one block per sentence, no host sync:
- * merges the per-row lists of vs_beam_topk into the 2*beam candidates (ties -> lowest beam*V+token),
+ * merges the per-row lists of vs_beam_topk (k = min(2*beam, V-1) entries each) into the reference's
+ * candidates -- k at step 0, min(2*beam, beam*V-1) later; ties -> lowest beam*V+token; beam <= 32 --,
  * finalizes eos hypotheses into fin_* ([bsz][beam][max_len+1] tokens / positional scores, score,
  * length), marks finished sentences (remaining[0] counts the others), picks the next beam's live
  * candidates, writes the gathered token / score rows (ping-pong buffers, row pitch max_len+2 /

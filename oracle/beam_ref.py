@@ -19,8 +19,8 @@ import numpy as np
 NEG_INF = -np.inf
 
 
-def log_softmax(x):
-    x = x.astype(np.float32)
+def log_softmax(x, dtype=np.float32):
+    x = x.astype(dtype)
     m = x.max(-1, keepdims=True)
     return (x - m) - np.log(np.exp(x - m).sum(-1, keepdims=True))
 
@@ -33,14 +33,17 @@ def topk_lowest_index(v, k):
 
 def generate(step_logits, bsz, vocab, pad, eos, unk, beam_size=1, max_len_a=0, max_len_b=200,
              min_len=1, normalize_scores=True, len_penalty=1.0, unk_penalty=0.0, temperature=1.0,
-             prefix_tokens=None, bos_token=None, src_len=1, max_decoder_positions=1024):
+             prefix_tokens=None, bos_token=None, src_len=1, max_decoder_positions=1024, dtype=np.float32,
+             trace=None):
     """step_logits(tokens [rows, step+1] int64, sent_ids [rows]) -> logits [rows, V] of the last
     position.  `sent_ids` = original sentence index of each row (rows shrink as sentences finish).
-    Returns finalized[sent] = list of dicts(tokens, score, positional_scores), best first."""
+    Returns finalized[sent] = list of dicts(tokens, score, positional_scores), best first.
+    `dtype`: the float type of the whole search (fp64 = the conditions of the parity tests); `trace`:
+    a list that receives every step's top k + 1 flattened scores [bsz, <= k + 1] (descending)."""
     beam_size = min(beam_size, vocab - 1)
     max_len = min(int(max_len_a * src_len + max_len_b), max_decoder_positions - 1)
     assert min_len <= max_len
-    scores = np.zeros((bsz * beam_size, max_len + 1), dtype=np.float32)
+    scores = np.zeros((bsz * beam_size, max_len + 1), dtype=dtype)
     tokens = np.full((bsz * beam_size, max_len + 2), pad, dtype=np.int64)
     tokens[:, 0] = eos if bos_token is None else bos_token
     cands_to_ignore = np.zeros((bsz, beam_size), dtype=bool)
@@ -56,7 +59,7 @@ def generate(step_logits, bsz, vocab, pad, eos, unk, beam_size=1, max_len_a=0, m
 
     for step in range(max_len + 1):
         logits = step_logits(tokens[:, : step + 1], sent_of_row)
-        lprobs = log_softmax(np.asarray(logits, dtype=np.float32) / np.float32(temperature))
+        lprobs = log_softmax(np.asarray(logits, dtype=dtype) / dtype(temperature), dtype)
         lprobs[lprobs != lprobs] = NEG_INF
         lprobs[:, pad] = NEG_INF
         lprobs[:, unk] -= unk_penalty
@@ -86,6 +89,8 @@ def generate(step_logits, bsz, vocab, pad, eos, unk, beam_size=1, max_len_a=0, m
             flat = (lp3 + scores.reshape(bsz, beam_size, -1)[:, :, step - 1][:, :, None]).reshape(bsz, -1)
         k = min(cand_size, flat.shape[1] - 1)
         cand_scores, cidx = topk_lowest_index(flat, k)
+        if trace is not None:
+            trace.append(topk_lowest_index(flat, k + 1)[0])
         cand_beams, cand_indices = cidx // vocab, cidx % vocab
         cand_bbsz_idx = cand_beams + bbsz_offsets
 
@@ -102,7 +107,7 @@ def generate(step_logits, bsz, vocab, pad, eos, unk, beam_size=1, max_len_a=0, m
             pos_scores[:, step] = eos_scores
             pos_scores[:, 1:] = pos_scores[:, 1:] - pos_scores[:, :-1]
             if normalize_scores:
-                eos_scores = eos_scores / np.float32((step + 1) ** len_penalty)
+                eos_scores = eos_scores / dtype((step + 1) ** len_penalty)
             cum_unfin, prev = [], 0
             for f in finished:
                 if f:
@@ -162,7 +167,7 @@ def generate(step_logits, bsz, vocab, pad, eos, unk, beam_size=1, max_len_a=0, m
         scores.reshape(bsz, beam_size, -1)[:, :, step] = np.take_along_axis(cand_scores, active_hypos, 1)
 
     for sent in range(len(finalized)):
-        sc = np.array([h["score"] for h in finalized[sent]], dtype=np.float32)
+        sc = np.array([h["score"] for h in finalized[sent]], dtype=dtype)
         order = np.argsort(-sc, kind="stable")
         finalized[sent] = [finalized[sent][i] for i in order]
     return finalized

@@ -69,8 +69,8 @@ def generate(step_logits, no_repeat_ngram_size, **kw):
 
     plain_lsm, plain_topk = beam_ref.log_softmax, beam_ref.topk_lowest_index
 
-    def banned_log_softmax(x):
-        lp = plain_lsm(x)
+    def banned_log_softmax(x, *dtype):
+        lp = plain_lsm(x, *dtype)
         toks = seen["tokens"]
         step = toks.shape[1] - 1
         for r in range(lp.shape[0] if n > 0 else 0):

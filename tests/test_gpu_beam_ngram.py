@@ -71,12 +71,14 @@ def _history(rs, V, n, step, L, targets):
 
 
 @pytest.mark.parametrize("n", [1, 2, 3, 4])
-@pytest.mark.parametrize("V", [1000, 5000, 50259])  # one block per row / 3 and 25 slices per row
+# one block per row / 3 and 25 slices per row; 2048 | 2049: the last one-block V and the first sliced one,
+# where the banned tokens 2047 and 2048 are the row's last (pad) and one past it | the two sides of the cut
+@pytest.mark.parametrize("V", [1000, 5000, 50259, 2048, 2049])
 def test_ngram_ban_kernel_rules(V, n, dev):
     from vidsitu_amd import ops
 
     x, cum, forced, lps, pad, eos, unk = _rules_inputs(V)
-    b = 2047 if V > 2048 else 31  # last token of a slice (of a bitmap word in the one-block kernel)
+    b = 2047 if V >= 2048 else 31  # last token of a slice (of a bitmap word in the one-block kernel)
     top = int(beam_ref.topk_lowest_index(lps[0] + cum[:, None], 1)[1][1, 0])  # row 1's best without a ban
     targets = [[b, b + 1, 5, V - 3],        # both sides of a boundary, several bans, several slices
                [top, 400],                  # the row's arg-max
@@ -97,9 +99,13 @@ def test_ngram_ban_kernel_rules(V, n, dev):
         if step + 2 - n < 0:
             assert not any(bans)
             saw["none"] = True
-        saw["many"] |= len(bans[0]) >= 3
-        saw["boundary"] |= b in bans[0] and b + 1 in bans[0]
-        saw["slices"] |= len({t // 2048 for t in bans[0]}) >= (2 if V > 2048 else 1)
+        # row 0's coverage is judged on what the kernel is handed, pad and ids >= V included: at V = 2048 | 2049
+        # the banned 2047 and 2048 are pad / out of range, and the kernel must still index its bitmaps right
+        raw0 = set(int(t) for t in R.banned_ref(hist[0], step, n))
+        assert set(bans[0]) == {t for t in raw0 if 0 <= t < V and t != pad}
+        saw["many"] |= len(raw0) >= 3
+        saw["boundary"] |= b in raw0 and b + 1 in raw0
+        saw["slices"] |= len({t // 2048 for t in raw0 if 0 <= t < V}) >= (2 if V > 2048 else 1)
         saw["top"] |= top in bans[1]
         saw["forced"] |= 42 in bans[2]
         # the device rows carry valid token ids after `step` (the search's buffers are uninitialised

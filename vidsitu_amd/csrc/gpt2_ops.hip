@@ -689,7 +689,9 @@ __global__ __launch_bounds__(256) void beam_lse_part_kernel(const float* logits,
 #pragma unroll
   for (int e = 0; e < BT_E; ++e) {
     const int j = sl * BT_SLICE + e * 256 + tid;
-    if (j < V) sum += expf(v[e] - mx);
+    // a -inf logit adds exactly 0; written out so that a slice of nothing but -inf (mx = -inf) gives 0 and
+    // not exp(-inf - -inf) = NaN, which would turn the whole row into -inf (a NaN logit still does)
+    if (j < V) sum += v[e] == -INFINITY ? 0.f : expf(v[e] - mx);
   }
   sum = wave_reduce_sum(sum);
   if ((tid & 63) == 0) red[tid >> 6] = sum;
@@ -1375,21 +1377,22 @@ __global__ __launch_bounds__(64) void beam_step_kernel(BeamStepP p) {
   }
   // ---- fairseq BeamSearch.step on the per-row lists: the csz best of beam*k entries, by value
   //      descending, ties towards the lowest flattened index beam*V + token (step 0: first beam only)
+  //      The reference keeps min(2*beam, entries - 1) candidates of the flattened scores: V - 1 = k at
+  //      step 0, beam*V - 1 later; the lists hold at least that many entries (beam <= V - 1).
   const int nb = p.step == 0 ? 1 : beam;
   const int total = nb * k;
+  const int ncand = p.step == 0 ? k : (int)min((long long)csz, (long long)beam * p.V - 1);
   float pv = INFINITY;
   long long pf = -1;
-  for (int c = 0; c < csz; ++c) {
+  for (int c = 0; c < ncand; ++c) {
     float bv = -INFINITY;
     long long bf = 0x7fffffffffffffffll;
     int bi = -1;
-    if (c < k) {
-      for (int e = lane; e < total; e += 64) {
-        const float v = p.row_val[row0 * k + e];
-        const long long f = (long long)(e / k) * p.V + p.row_idx[row0 * k + e];
-        const bool after = (v < pv) || (v == pv && f > pf);
-        if (after && (v > bv || (v == bv && f < bf))) { bv = v; bf = f; bi = e; }
-      }
+    for (int e = lane; e < total; e += 64) {
+      const float v = p.row_val[row0 * k + e];
+      const long long f = (long long)(e / k) * p.V + p.row_idx[row0 * k + e];
+      const bool after = (v < pv) || (v == pv && f > pf);
+      if (after && (v > bv || (v == bv && f < bf))) { bv = v; bf = f; bi = e; }
     }
     bestv[lane] = bv; bestf[lane] = bf; besti[lane] = bi;
     __syncthreads();
@@ -1405,7 +1408,7 @@ __global__ __launch_bounds__(64) void beam_step_kernel(BeamStepP p) {
     if (lane == 0) {
       if (besti[0] >= 0) {
         cv[c] = bestv[0]; ct[c] = (int)p.row_idx[row0 * k + besti[0]]; cb[c] = besti[0] / k;
-      } else {  // fewer than 2*beam candidates exist (tiny vocabularies): -inf padding
+      } else {  // unreachable for lists of distinct tokens (total >= ncand); keeps cv/ct/cb defined
         cv[c] = -INFINITY; ct[c] = 0; cb[c] = 0;
       }
     }
@@ -1434,7 +1437,12 @@ __global__ __launch_bounds__(64) void beam_step_kernel(BeamStepP p) {
         }
         fp[p.step] = p.step == 0 ? cv[c] : cv[c] - prev;
         float sc = cv[c];
-        if (p.normalize) sc = sc / powf((float)(p.step + 1), p.len_penalty);
+        if (p.normalize) {
+          // the reference divides by the correctly rounded power; powf is 1 ulp off for some lengths even
+          // where the power is exact (41^1), so the exact cases -- 1 is the default -- do not go through it
+          const float len = (float)(p.step + 1);
+          sc = sc / (p.len_penalty == 1.f ? len : p.len_penalty == 0.f ? 1.f : powf(len, p.len_penalty));
+        }
         p.fin_score[s * beam + h] = sc;
         p.fin_len[s * beam + h] = p.step + 1;
       }
@@ -1461,7 +1469,7 @@ __global__ __launch_bounds__(64) void beam_step_kernel(BeamStepP p) {
   if (lane == 0) {
     int n = 0;
     for (int pass = 0; pass < 2 && n < beam; ++pass)
-      for (int c = 0; c < csz && n < beam; ++c) {
+      for (int c = 0; c < ncand && n < beam; ++c) {
         bool dead = ct[c] == p.eos && cv[c] != -INFINITY;
         if (c < beam) dead = dead || p.ignore[s * beam + c];
         if ((pass == 0) == !dead) act[n++] = c | (dead ? 0x10000 : 0);

@@ -16,6 +16,7 @@ best first).  Differences, all deliberate:
   a per-step copy of the token matrix to the host and a Python dict of n-grams per row.  n = 1 is
   refused: the reference then bans every token of the row including `tokens[:, 0]` = eos, so no
   hypothesis can finish and its own `assert step < max_len` fires;
+* `beam_size` > 16 is refused: a step asks the scoring kernel for 2*beam entries per row and its lists hold 32;
 * a single model (the reference never passes more than one), no `match_source_len`, no constraints /
   lm_model (unused by the reference's configs: they raise).
 """
@@ -222,11 +223,15 @@ class SeqGenCustom(nn.Module):
                 "no_repeat_ngram_size must be 0 or >= 2: with 1 the reference bans every token of the row, "
                 "tokens[:, 0] = eos included, so no hypothesis can ever finish (seq_gen.py:739-772)")
         self.no_repeat_ngram_size = int(no_repeat_ngram_size)
+        if self.beam_size > 16:
+            raise NotImplementedError(
+                "beam_size > 16: every step asks the scoring kernel (vs_beam_topk) for 2*beam entries per "
+                "row and its lists hold at most 32")
         self.use_kv_cache = use_kv_cache
         # device_search: the bookkeeping between two decoder calls runs in one kernel per step
         # (vs_beam_step) with a host sync every 8 steps only; False = the torch-op mirror of the
         # reference's host loop below (one or more syncs per step)
-        self.device_search = device_search and self.beam_size <= 32
+        self.device_search = device_search
         self.model.eval()
 
     @torch.no_grad()
@@ -338,16 +343,14 @@ class SeqGenCustom(nn.Module):
                 cand_scores, cand_indices = rv[:, 0, :], ri[:, 0, :]
                 cand_beams = torch.zeros_like(cand_indices)
             else:
+                # the reference's count: min(2*beam, beam*V - 1) of the flattened scores; more than the
+                # k = V - 1 of a row's list where V <= 2*beam (tiny vocabularies)
+                ncand = min(cand_size, beam * V - 1)
                 flat_v = rv.reshape(bsz, beam * k)
-                order = torch.sort(flat_v, dim=1, descending=True, stable=True)[1][:, :k]
+                order = torch.sort(flat_v, dim=1, descending=True, stable=True)[1][:, :ncand]
                 cand_scores = flat_v.gather(1, order)
                 cand_indices = ri.reshape(bsz, beam * k).gather(1, order)
                 cand_beams = order // k
-            if k < cand_size:  # tiny vocabularies only
-                padn = cand_size - k
-                cand_scores = torch.cat([cand_scores, cand_scores.new_full((bsz, padn), -math.inf)], 1)
-                cand_indices = torch.cat([cand_indices, cand_indices.new_zeros((bsz, padn))], 1)
-                cand_beams = torch.cat([cand_beams, cand_beams.new_zeros((bsz, padn))], 1)
             cand_bbsz_idx = cand_beams + bbsz_offsets
 
             eos_mask = cand_indices.eq(self.eos) & cand_scores.ne(-math.inf)

@@ -123,13 +123,13 @@ int vs_conv_fwd(const void* x, const void* w, void* y, const vs_conv_desc* d, co
                 const float* shift, const void* residual, float* stats_partial,
                 void* workspace, size_t ws_bytes, void* stream);
 int vs_conv_stats_rows(const vs_conv_desc* d);
-/* The size queries (vs_conv_stats_rows, vs_conv_dgrad_bnstats_rows, vs_conv_aol_ok) and the launches decide which
+/* The size queries (vs_conv_stats_rows, vs_conv_dgrad_bnstats_rows) and the launches decide which
  * kernel runs through one function: a buffer sized by a query is written by the launch that gets the SAME descriptor,
  * flags included.
  * Split-K workspace (few-tile, deep-K layers); 0 when the TILE kernel's plan for this shape has no split.  It is an
  * upper bound: the answer is the tile kernel's need also where another kernel (halo-image, pointwise, deep-pipeline:
  * no workspace) takes the plain launch, because the descriptor does not carry the launch state (BN-backward sums of
- * two units, apply on load) that sends a convolution back to the tile kernel.
+ * two units) that sends a convolution back to the tile kernel.
  * dgrad = 1 sizes the workspace of vs_conv_dgrad for the same descriptor.
  * The buffer's head holds one arrival counter per tile for the in-launch split plan: it has to be ZERO before the first
  * launch that uses the buffer and belongs to the library from then on (every launch leaves the counters at zero);
@@ -141,25 +141,10 @@ size_t vs_conv_workspace_bytes(const vs_conv_desc* d, int dgrad);
  * out[0..1] its tile, out[2] its weight-ring depth, out[3] its unrolled tap count; out[4] == 3: the persistent
  * pointwise kernel (conv_pw.hip); out[4] == 4: the deep-pipeline kernel (conv_deep.hip: 256 x 256 tile, out[2] = 8
  * LDS sub-buffers); out[4] == 5: the tile kernel with out[3] blocks per tile and the in-launch split-K sum.
- * It answers for the PLAIN launch (vs_conv_fwd / vs_conv_dgrad): BN-backward sums and apply on load are arguments of
+ * It answers for the PLAIN launch (vs_conv_fwd / vs_conv_dgrad): BN-backward sums are arguments of
  * the launch, not part of the descriptor, and may move a convolution to another kernel.  VS_CONV_NAIVE, and strides a
  * data gradient refuses (not powers of two): the tile kernel's plan for the shape.  Profiling / attribution only. */
 int vs_conv_plan(const vs_conv_desc* d, int dgrad, int* out);
-/* Apply on load (training, the b -> c edge of a bottleneck: slowfast resnet_helper.BottleneckTransform.forward
- * `x = self.b_relu(self.b_bn(x)); x = self.c(x)`): the 1x1x1 convolution takes the PRODUCER unit's raw convolution
- * output x and that unit's batch-norm constants (vs_bn_finalize's scale / shift) and multiplies
- * relu(x * in_scale[c] + in_shift[c]) rounded to bf16 -- bit for bit the tensor vs_bn_apply would have stored, formed
- * on the operand fragments and never written.  vs_conv_fwd_aol: epilogue VS_CONV_STATS only; vs_conv_wgrad_aol: the
- * weight gradient of the same convolution (dy, x as in vs_conv_wgrad).  The *_ok queries say for which descriptors
- * the plan lands on a kernel with the transform (1x1x1, unit stride, Cin <= 512; forward: the persistent pointwise
- * kernel's 128-column variant or the 128 x 128 two-stage-ring tile; weight gradient: the 128-row ring tiles); a caller
- * materialises the activation with vs_bn_apply where they return 0. */
-int vs_conv_aol_ok(const vs_conv_desc* d);
-int vs_conv_fwd_aol(const void* x, const void* w, void* y, const vs_conv_desc* d, const float* in_scale,
-                    const float* in_shift, float* stats_partial, void* stream);
-int vs_conv_wgrad_aol_ok(const vs_conv_desc* d);
-int vs_conv_wgrad_aol(const void* dy, const void* x, float* dw, const vs_conv_desc* d, const float* in_scale,
-                      const float* in_shift, void* workspace, size_t ws_bytes, void* stream);
 /* Evaluation: conv b (+ folded BN + ReLU) and conv c (1x1x1, + folded BN + residual + ReLU) of a fast-pathway
  * bottleneck in ONE launch -- slowfast resnet_helper.BottleneckTransform.forward (b, b_bn, b_relu, c, c_bn) and
  * ResBlock.forward's `x + f(x)` / relu for the blocks whose inner width is 8, 16 or 32 channels (SlowFast-R50 fast

@@ -3,7 +3,7 @@ batch size, and the ratio of the per-clip costs (1.0 = scales with the batch; 4.
 import csv, re, sys
 
 STEPS = 7  # bench.py --steps 5 --warmup 2 (eager: every step is profiled)
-FAM = [("conv fwd/dgrad (igemm)", r"conv_igemm_kernel|conv_igemm_aol"), ("conv halo", r"conv_halo"), ("conv pw", r"conv_pw_kernel"),
+FAM = [("conv fwd/dgrad (igemm)", r"conv_igemm_kernel"), ("conv halo", r"conv_halo"), ("conv pw", r"conv_pw_kernel"),
        ("conv deep", r"conv_deep_kernel"), ("conv direct", r"conv_direct"), ("conv pair (dgrad+wgrad)", r"conv_pair_kernel"),
        ("wgrad deep", r"conv_wgrad_deep"), ("wgrad ring/tile", r"conv_wgrad_kernel|conv_wgrad_ring"),
        ("wgrad reduce / bn-bwd finalize", r"wgrad_reduce|bn_bwd_finalize|bn_finalize2"),

@@ -7,7 +7,7 @@ import sys
 src = sys.argv[1]
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
 cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Iinclude",
-       "-mllvm", "-amdgpu-mfma-vgpr-form=1", "-c", src, "-o", "/dev/null",
+       "-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize", "-c", src, "-o", "/dev/null",
        "-Rpass-analysis=kernel-resource-usage"]
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 cur = None

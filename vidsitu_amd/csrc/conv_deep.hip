@@ -478,10 +478,10 @@ static size_t deep_smem_bytes(int K) {
 
 // Does this launch run on the deep-pipeline kernel?  mode: kernel MODE (0 pointwise, 1 gather; the transposed gather
 // of strided data gradients stays on the tile kernel).
-bool vs_deep_plan(const ConvP& p, int mode, int flags, bool aol, bool two_units, DeepGeo* out) {
+bool vs_deep_plan(const ConvP& p, int mode, int flags, bool two_units, DeepGeo* out) {
   if (!deep_mode() || mode < 0 || mode > 1 || (flags & VS_CONV_NODEEP)) return false;
   if (((flags >> 8) & 0xf) != 0 || (flags & ((7 << 12) | VS_CONV_SPLITK | (7 << 16)))) return false;  // forced plan / debug
-  if (aol || two_units) return false;  // apply on load, two-unit sums: tile kernel only
+  if (two_units) return false;  // two-unit sums: tile kernel only
   const int taps = p.kT * p.kH * p.kW;
   if (taps > 31 || p.Cg % 8 != 0 || p.Ncols % 8 != 0) return false;
   if (p.K > 8 * 2048) return false;  // table size

@@ -39,10 +39,8 @@ struct ConvSmem {
 // (`buffer_load_dwordx4 ... lds`, NS-1 tiles in flight, one raw barrier per k-step).
 // BNB: the dgrad variant that also emits the consumer BN's backward sums (VS_CONV_BNBWD); a template flag
 // so that the extra epilogue registers do not count against every other launch's occupancy.
-// AOL (MODE 0 ring launches only): apply on load, see ConvP::in_scale -- the constants of the input channels live in
-// LDS behind the statistic rows, every A fragment goes through aol_frag_k after its LDS read.
 template <int BM, int BN, int WM, int WN, int MODE, bool FAST, int DBG = 0, int NS = 0, bool BNB = false,
-          bool BNB2 = false, bool AOL = false>
+          bool BNB2 = false>
 __device__ __forceinline__ void conv_igemm_body(const ConvP& p, const int blk, const int nblk) {
   // (blk / nblk: this block's index and the block count of THIS convolution's grid -- blockIdx.x / gridDim.x of the
   //  stand-alone launch, a sub-range of the grid in the dgrad + wgrad pair launch of conv_pair.hip)
@@ -54,7 +52,6 @@ __device__ __forceinline__ void conv_igemm_body(const ConvP& p, const int blk, c
   constexpr int STAGE = ConvSmem<BM, BN>::STAGE;
   constexpr int MAIN = ConvSmem<BM, BN, (NS > 2 ? NS : 2)>::MAIN;
   static_assert(NS == 0 || (FAST && NS >= 2 && BN >= 32), "LDS-DMA ring needs the FAST gather");
-  static_assert(!AOL || (MODE == 0 && NS >= 2), "apply on load: pointwise ring launches");
   static_assert(WM * WN == 4, "4 waves");
   static_assert(TM % 16 == 0 && TN % 16 == 0, "wave tile");
 
@@ -260,7 +257,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvP& p, const int blk, c
   // (1.0 us on a pointwise one).  The gathering launches now decode ONE row per thread into an LDS table (aliased
   // on the statistic rows, which only the epilogue uses) and every thread picks up its AI entries behind the barrier
   // the k-table needs anyway: AI x fewer decode instructions per wave, same integers.
-  constexpr bool ROWTAB = FAST && !AOL && BM <= 256;
+  constexpr bool ROWTAB = FAST && BM <= 256;
   static_assert(8 * WM * BN * 4 >= BM * 8, "the row table fits the statistic rows it is aliased on");
   const bool use_rowtab = ROWTAB && !(MODE == 0 && p.dense);
   uint2* rowtab = (uint2*)statbuf;  // [BM] (roff, vmask)
@@ -394,17 +391,6 @@ __device__ __forceinline__ void conv_igemm_body(const ConvP& p, const int blk, c
 
   // straight-line MFMA chains (no conditional exit: a branch here makes the compiler shuttle
   // every accumulator between AGPRs and VGPRs each k-step); a K tail multiplies staged zeros.
-  // AOL: [2][AOL_K] scale / shift of input channel k behind the statistic rows (MODE 0: no tables there); aol_k0 =
-  // first channel of the k-tile `compute` is about to multiply
-  constexpr int AOL_K = 512;
-  float* aol_tab = (float*)(smem + MAIN + 8 * WM * BN * 4);
-  int aol_k0 = 0;
-  if (AOL) {
-    for (int i = tid; i < AOL_K; i += 256) {
-      aol_tab[i] = i < p.K ? p.in_scale[i] : 0.f;
-      aol_tab[AOL_K + i] = i < p.K ? p.in_shift[i] : 0.f;
-    }  // (published by the ring loop's first barrier)
-  }
   auto compute = [&](int buf) __attribute__((always_inline)) {
     const char* A = smem + buf * STAGE;
     const char* B = A + BM * 128;
@@ -417,10 +403,6 @@ __device__ __forceinline__ void conv_igemm_body(const ConvP& p, const int blk, c
         const int row = wm * TM + a * 16 + lr;
         if (DBG == 4) af[a] = __builtin_bit_cast(bf16x8, (u32x4){(unsigned)row, (unsigned)ch, 1u, 2u});
         else af[a] = *(const bf16x8*)(A + row * 128 + ((ch ^ ((row >> 1) & 7)) << 4));
-        if (AOL) {  // rows past M were zero-filled and have to stay zero (the statistic partials sum every tile row)
-          const bf16x8 t = aol_frag_k(af[a], aol_tab + aol_k0 + ch * 8, aol_tab + AOL_K + aol_k0 + ch * 8);
-          af[a] = (m0 + row < p.M) ? t : __builtin_bit_cast(bf16x8, make_uint4(0u, 0u, 0u, 0u));
-        }
       }
 #pragma unroll
       for (int b = 0; b < NR; ++b) {
@@ -573,7 +555,6 @@ __device__ __forceinline__ void conv_igemm_body(const ConvP& p, const int blk, c
       dma_e(kbeg + kt + D, st_l, e_next);
       if (MODE != 0) e_next = ktab[(kbeg + kt + D + 1) * 8 + kce];  // (the table is padded one k-step past the ring's run-ahead)
       __builtin_amdgcn_sched_barrier(0);
-      if (AOL) aol_k0 = (kbeg + kt) * 64;
       compute(st_c);
       __builtin_amdgcn_sched_barrier(0);
       st_c = (st_c + 1 == NS) ? 0 : st_c + 1;
@@ -623,7 +604,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvP& p, const int blk, c
 
   VS_ST(vst, 3);
   bool in_launch = false;
-  if constexpr (NS >= 2 && !AOL) {
+  if constexpr (NS >= 2) {
     if (p.splitK > 1 && p.sk_cnt != nullptr) {
       // In-launch split-K: the S blocks of a tile (neighbours in the block order, same XCD run) each store their fp32
       // partial accumulators -- in register order, one 4-KiB row of float4 per (a, b) fragment, nothing staged -- and
@@ -722,12 +703,6 @@ template <int BM, int BN, int WM, int WN, int MODE, bool FAST, int DBG = 0, int 
           bool BNB2 = false>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvP p) {
   conv_igemm_body<BM, BN, WM, WN, MODE, FAST, DBG, NS, BNB, BNB2>(p, blockIdx.x, gridDim.x);
-}
-
-// Apply on load (ConvP::in_scale): the pointwise ring launch whose A fragments go through the producer's BN + ReLU.
-template <int BM, int BN, int WM, int WN, int NS>
-__global__ __launch_bounds__(256) void conv_igemm_aol_kernel(ConvP p) {
-  conv_igemm_body<BM, BN, WM, WN, 0, true, 0, NS, false, false, true>(p, blockIdx.x, gridDim.x);
 }
 
 // Sum of the split-K slabs (fixed order) + the whole fused epilogue.  Block = 64 rows x all
@@ -1695,20 +1670,14 @@ static void setup_stride_classes(ConvP& p, int bm, int mode, int flags) {
   }
 }
 
-// the tile-kernel launch apply on load is built for: pointwise, the 128 x 128 tile on the 2-stage ring, no split-K
-static bool aol_tile_ok(const ConvPlan& pl, int mode, int K) {
-  return mode == 0 && !pl.direct && pl.S == 1 && pl.tile.bm == 128 && pl.tile.bn == 128 && pl.ring == 2 && K <= 512;
-}
-
 // ---- which kernel runs a forward convolution or a data gradient: ONE decision -------------------------------------
 enum ConvKind { CONV_NAIVE, CONV_HALO, CONV_PW, CONV_DEEP, CONV_DIRECT, CONV_TILE, CONV_SPLITK, CONV_SPLITK_IL };
 
 // What a launch knows beyond its geometry and the descriptor's flags.  The launch reads it off its arguments; a query
-// states it (vs_conv_dgrad_bnstats_rows: bnb; vs_conv_aol_ok: aol; everything else: none).
+// states it (vs_conv_dgrad_bnstats_rows: bnb; everything else: none).
 struct ConvState {
   bool bnb;   // dgrad that emits BN-backward sums (VS_CONV_BNBWD)
   bool bnb2;  // ... of a second unit beside the first (vs_dgrad_epilogue.bn_y2)
-  bool aol;   // forward with apply on load (vs_conv_fwd_aol)
 };
 
 // Only the geometry member that `kind` names is valid (the others are zero); read it under a test or a switch on `kind`.
@@ -1722,7 +1691,6 @@ struct ConvChoice {
   // blocks of the epilogue kernel under CONV_SPLITK; before the stride classes of a strided data gradient
   // (setup_stride_classes renumbers them).  CONV_NAIVE writes none: the displaced plan's figure.
   int tilesM;
-  bool aol_ok;  // an apply-on-load variant of this kernel exists
 };
 
 // The tile kernel's part of the choice: small-channel kernel, tile, split-K, in-launch split-K.
@@ -1751,21 +1719,17 @@ static ConvChoice choose_conv(const ConvP& p, int mode, int flags, ConvState s) 
     if (vs_pw_plan(p, mode, flags, s.bnb, &c.pg)) {  // shallow-K pointwise: persistent weight-resident kernel
       c.kind = CONV_PW;
       c.tilesM = c.pg.tilesM;
-      c.aol_ok = vs_pw_aol_ok(c.pg, p.K, s.bnb);
       return c;
     }
     // wide, deep reductions that fill the chip with 256 x 256 tiles
-    if (vs_deep_plan(p, mode, flags, s.aol, s.bnb2 || (flags & VS_CONV_BNB2), &c.dg)) {
+    if (vs_deep_plan(p, mode, flags, s.bnb2 || (flags & VS_CONV_BNB2), &c.dg)) {
       c.kind = CONV_DEEP;
       c.tilesM = c.dg.tilesM;
       return c;
     }
   }
   c = choose_tile(p.M, p.Ncols, p.K, p.kT * p.kH * p.kW, flags);
-  if (flags & VS_CONV_NAIVE)
-    c.kind = CONV_NAIVE;
-  else
-    c.aol_ok = aol_tile_ok(c.pl, mode, p.K);
+  if (flags & VS_CONV_NAIVE) c.kind = CONV_NAIVE;
   return c;
 }
 
@@ -1779,13 +1743,8 @@ static int launch_conv(ConvP& p, int mode, int flags, void* ws, size_t ws_bytes,
   p.splitK = 1;
   p.slab = nullptr;
   p.sk_cnt = nullptr;
-  const ConvChoice ch =
-      choose_conv(p, mode, flags, {(p.flags & VS_CONV_BNBWD) != 0, p.bny2 != nullptr, p.in_scale != nullptr});
+  const ConvChoice ch = choose_conv(p, mode, flags, {(p.flags & VS_CONV_BNBWD) != 0, p.bny2 != nullptr});
   const ConvPlan& pl = ch.pl;
-  if (p.in_scale && !ch.aol_ok) {  // apply on load: vs_conv_aol_ok told the caller which launches exist
-    vs_set_error("conv: apply on load is not built for this plan (ask vs_conv_aol_ok)");
-    return VS_ERR_UNSUPPORTED;
-  }
   switch (ch.kind) {
     case CONV_NAIVE: {
       const long long total = (long long)p.M * p.Ncols;
@@ -1814,17 +1773,6 @@ static int launch_conv(ConvP& p, int mode, int flags, void* ws, size_t ws_bytes,
   const TileCfg c = pl.tile;
   p.tilesM = (p.M + c.bm - 1) / c.bm;
   p.tilesN = (p.Ncols + c.bn - 1) / c.bn;
-  if (p.in_scale) {
-    static std::once_flag attr;
-    std::call_once(attr, [] {
-      (void)hipFuncSetAttribute((const void*)conv_igemm_aol_kernel<128, 128, 2, 2, 2>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
-    const size_t smem = conv_smem_bytes(128, 128, 2, 2, 0, p.K) + 2 * 512 * sizeof(float);
-    hipLaunchKernelGGL((conv_igemm_aol_kernel<128, 128, 2, 2, 2>), dim3(p.tilesM * p.tilesN), dim3(256), smem, st, p);
-    VS_CHECK_LAUNCH();
-    return VS_OK;
-  }
   setup_stride_classes(p, c.bm, mode, flags);
   if (ch.kind == CONV_SPLITK_IL) {
     if (ws == nullptr || ws_bytes < plan_ws_bytes(pl, p.M, p.Ncols)) {
@@ -1946,7 +1894,7 @@ extern "C" int vs_conv_stats_rows(const vs_conv_desc* d) {
   return choose_conv(p, mode, d->flags, {}).tilesM;
 }
 
-// The plan of the plain launch: no BN-backward sums, no second unit, no apply on load (the descriptor carries none).
+// The plan of the plain launch: no BN-backward sums, no second unit (the descriptor carries none).
 extern "C" int vs_conv_plan(const vs_conv_desc* d, int dgrad, int* out) {
   VS_CHECK_ARG(d != nullptr && out != nullptr, "null argument");
   const int taps = d->kT * d->kH * d->kW;
@@ -1988,7 +1936,7 @@ extern "C" int vs_conv_plan(const vs_conv_desc* d, int dgrad, int* out) {
 }
 
 // The TILE plan's need, whichever earlier stage would take the launch: an upper bound.  The descriptor does not carry
-// the launch state (BN sums of two units, apply on load) that sends a convolution back to the tile kernel, so the
+// the launch state (BN sums of two units) that sends a convolution back to the tile kernel, so the
 // answer must cover that kernel for every descriptor; the earlier stages need no workspace.
 extern "C" size_t vs_conv_workspace_bytes(const vs_conv_desc* d, int dgrad) {
   const int taps = d->kT * d->kH * d->kW;
@@ -2017,46 +1965,6 @@ extern "C" int vs_conv_fwd(const void* x, const void* w, void* y, const vs_conv_
   p.stats = stats_partial;
   VS_CHECK_ARG(set_extents(p), "tensor larger than 2 GiB");
   return launch_conv(p, mode, d->flags, workspace, ws_bytes, (hipStream_t)stream);
-}
-
-// Apply on load (train, the b -> c edge of a bottleneck): which forward convolutions can take their input as the
-// producer unit's RAW output plus that unit's BN scale / shift (vs_conv_fwd_aol), i.e. for which descriptors the plan
-// lands on a kernel with the fragment transform: 1x1x1, unit stride, Cin <= 512, on the persistent pointwise kernel
-// (128-column variant) or the 128 x 128 tile on the two-stage ring.
-extern "C" int vs_conv_aol_ok(const vs_conv_desc* d) {
-  if (check_desc(d) != VS_OK) return 0;
-  if (d->flags & (VS_CONV_NAIVE | VS_CONV_AFFINE | VS_CONV_RESIDUAL | VS_CONV_RELU)) return 0;
-  ConvP p{};
-  const int mode = fill_fwd_params(p, d);
-  if (mode != 0 || !p.dense || p.K > 512 || p.K % 8) return 0;
-  // The apply-on-load launch never runs on the deep-pipeline kernel, but vs_conv_stats_rows (which knows of no apply
-  // on load) would size the statistic rows for it (256-row tiles) while the 128-row tile kernel writes twice as many:
-  // a descriptor whose plain launch lands elsewhere is refused here -- callers pass VS_CONV_NODEEP so that the rows
-  // query and the launch agree.
-  const ConvChoice c = choose_conv(p, mode, d->flags, {false, false, true});
-  return (c.aol_ok && c.kind == choose_conv(p, mode, d->flags, {}).kind) ? 1 : 0;
-}
-
-// y = conv1x1(relu(x * in_scale[c] + in_shift[c]), w) with x the producer's raw convolution output: the operand is
-// what vs_bn_apply(x, in_scale, in_shift, relu) would have written, bit for bit, never stored.  Epilogue: VS_CONV_STATS
-// only (the train-mode c unit).  Replaces `b_relu(b_bn(.))` -> `c(.)` of slowfast BottleneckTransform.forward.
-extern "C" int vs_conv_fwd_aol(const void* x, const void* w, void* y, const vs_conv_desc* d, const float* in_scale,
-                               const float* in_shift, float* stats_partial, void* stream) {
-  int rc = check_desc(d);
-  if (rc) return rc;
-  VS_CHECK_ARG(x && w && y && in_scale && in_shift, "null tensor");
-  VS_CHECK_ARG(vs_conv_aol_ok(d), "apply on load is not built for this convolution: ask vs_conv_aol_ok");
-  VS_CHECK_ARG(!(d->flags & VS_CONV_STATS) || stats_partial, "STATS needs stats_partial");
-  ConvP p{};
-  const int mode = fill_fwd_params(p, d);
-  p.x = (const uint16_t*)x;
-  p.w = (const uint16_t*)w;
-  p.y = (uint16_t*)y;
-  p.stats = stats_partial;
-  p.in_scale = in_scale;
-  p.in_shift = in_shift;
-  VS_CHECK_ARG(set_extents(p), "tensor larger than 2 GiB");
-  return launch_conv(p, mode, d->flags, nullptr, 0, (hipStream_t)stream);
 }
 
 // conv b -> conv c of a bottleneck in one launch (evaluation): which (descriptor of conv b, width of conv c) pairs
@@ -2199,7 +2107,7 @@ extern "C" int vs_conv_dgrad_bnstats_rows(const vs_conv_desc* d) {
   // a strided dgrad with a residual: tiles of stride classes no tap reaches copy the residual without
   // passing through the epilogue
   if ((d->flags & VS_CONV_RESIDUAL) && mode == 2) return 0;
-  const ConvChoice c = choose_conv(p, mode, d->flags, {true, (d->flags & VS_CONV_BNB2) != 0, false});
+  const ConvChoice c = choose_conv(p, mode, d->flags, {true, (d->flags & VS_CONV_BNB2) != 0});
   if (c.kind == CONV_DIRECT) {
     // The small-channel kernel can emit them too (one partial row per block), but it is bound by instruction
     // issue, not by bandwidth: with the mask / sum arithmetic in its copy-out the step is 0.1-0.2 ms SLOWER

@@ -36,9 +36,7 @@ __device__ __forceinline__ void pw_wait_vm(int n) {
   }
 }
 
-// AOL: the activation operand is the producer's raw convolution output, BN + ReLU applied to every A fragment after
-// its LDS read (ConvP::in_scale / in_shift; the constants of the <= 128 input channels sit behind the statistic rows).
-template <int BN, bool BNB, int EDBG = 0, bool AOL = false>
+template <int BN, bool BNB, int EDBG = 0>
 __global__ __launch_bounds__(256) void conv_pw_kernel(ConvP p, PwGeo g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int BM = PW_BM;
@@ -73,13 +71,6 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(ConvP p, PwGeo g) {
   char* ring = smem + b_bytes;
   char* epi = ring + g.nslot * PW_SLOT;
   float* statbuf = (float*)(epi + g.epi_bytes);
-  float* aol_tab = (float*)((char*)statbuf + 4096);  // [2][128]: scale, shift of input channel k (zero beyond K)
-  if (AOL) {
-    if (tid < 128) {
-      aol_tab[tid] = tid < p.K ? p.in_scale[tid] : 0.f;
-      aol_tab[128 + tid] = tid < p.K ? p.in_shift[tid] : 0.f;
-    }  // (published by the first chunk's barrier)
-  }
 
   typedef __attribute__((address_space(3))) char* lds_ptr_t;
   const int wv = __builtin_amdgcn_readfirstlane(wave);
@@ -154,7 +145,6 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(ConvP p, PwGeo g) {
 #endif
 
   f32x4 acc[MR][NR];
-  int m0c = 0;  // first row of the tile `compute` works on (AOL)
   auto compute = [&](int slot, int kch) __attribute__((always_inline)) {
     const char* A = ring + slot * PW_SLOT;
     const char* B = Bl + kch * BN * 128;
@@ -166,10 +156,6 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(ConvP p, PwGeo g) {
       for (int a = 0; a < MR; ++a) {
         const int row = wm * TM + a * 16 + lr;
         af[a] = *(const bf16x8*)(A + row * 128 + ((ch ^ ((row >> 1) & 7)) << 4));
-        if (AOL) {  // rows past M were zero-filled and have to stay zero (the statistic partials sum every tile row)
-          const bf16x8 t = aol_frag_k(af[a], aol_tab + kch * 64 + ch * 8, aol_tab + 128 + kch * 64 + ch * 8);
-          af[a] = (m0c + row < p.M) ? t : __builtin_bit_cast(bf16x8, make_uint4(0u, 0u, 0u, 0u));
-        }
       }
 #pragma unroll
       for (int b = 0; b < NR; ++b) {
@@ -189,7 +175,6 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(ConvP p, PwGeo g) {
   for (int ti = 0; ti < ntl; ++ti) {
     const int tm = gid + ti * g.ngroups;
     const int m0 = tm * BM;
-    m0c = m0;
 #pragma unroll
     for (int a = 0; a < MR; ++a)
 #pragma unroll
@@ -253,7 +238,8 @@ bool vs_pw_plan(const ConvP& p, int mode, int flags, bool bnb, PwGeo* out) {
   const bool has_res = (p.flags & VS_CONV_RESIDUAL) != 0;
   // (bf16 staging tile: row pitch bn + 8 elements, see conv_tile_epilogue)
   g.epi_bytes = has_res ? PW_BM * g.bn * 4 : (bnb ? PW_BM * (g.bn + 8) * 2 + 16384 : PW_BM * (g.bn + 8) * 2);
-  // + statbuf [2][4 * WM][BN] = 4 KB for both variants (WM * BN = 128) + 1 KB: apply-on-load constants [2][128]
+  // + statbuf [2][4 * WM][BN] = 4 KB for both variants (WM * BN = 128) + 1 KB that no kernel reads any more: the budget
+  // of every variant was measured with it, and dropping it moves smem, the slot count and the two-blocks-per-CU test
   const int fixed = g.nk * g.bn * 128 + g.epi_bytes + 4096 + 1024;
   // Measured (profiles/r02_pw_ab.txt): a block's epilogue is ~1 us of serial VALU / LDS work per tile and only a
   // second resident block hides it -- one block per CU loses to the tile kernel at every shape, a deeper ring
@@ -308,30 +294,8 @@ static int pw_launch_edbg(const ConvP& p, const PwGeo& g, hipStream_t st) {
   return VS_OK;
 }
 
-static int pw_launch_aol(const ConvP& p, const PwGeo& g, hipStream_t st) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)conv_pw_kernel<128, false, 0, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((conv_pw_kernel<128, false, 0, true>), dim3(8 * g.nsl * g.gx), dim3(256), g.smem, st, p, g);
-  VS_CHECK_LAUNCH();
-  return VS_OK;
-}
-
-// apply on load is built for the 128-column variant without the BN-backward-sums epilogue (the c units' forward)
-bool vs_pw_aol_ok(const PwGeo& g, int K, bool bnb) { return g.bn == 128 && !bnb && K <= 128; }
-
 int vs_pw_launch(const ConvP& p, const PwGeo& g, hipStream_t st) {
   const bool bnb = (p.flags & VS_CONV_BNBWD) != 0;
-  if (p.in_scale) {
-    if (!vs_pw_aol_ok(g, p.K, bnb)) {
-      vs_set_error("conv_pw: apply on load is not built for this variant");
-      return VS_ERR_UNSUPPORTED;
-    }
-    return pw_launch_aol(p, g, st);
-  }
   static const int edbg = pw_env("VS_PW_EDBG", 0);  // epilogue ablations (tools only): 1 no statistics, 2 no staging writes
   if (edbg && g.bn == 128 && !bnb) {
     if (edbg == 1) return pw_launch_edbg<1>(p, g, st);

@@ -66,11 +66,6 @@ struct ConvP {
   const float *bn_mean2, *bn_invstd2;
   float* stats2;
   int bny2_ld;
-  // Apply on load (train, the b -> c edge of a bottleneck): x is the PRODUCER unit's raw convolution output and the
-  // operand is relu(x * in_scale[c] + in_shift[c]) rounded to bf16 -- what vs_bn_apply would have written, bit for
-  // bit, formed on the A fragments after their LDS read.  NULL: x is used as it is.
-  const float* in_scale;
-  const float* in_shift;
 #ifdef VS_STAMP
   unsigned long long* stamp;  // diagnostic build only (tools/launch_anatomy.py): [block][8] s_memrealtime stamps, or NULL
 #endif
@@ -514,8 +509,8 @@ struct HaloGeo {
 
 
 // The three plans below are stages of choose_conv (conv_igemm.hip), their only caller: it has already turned
-// VS_CONV_NAIVE away, and it passes the launch state they depend on (bnb: the dgrad emits BN-backward sums; aol: apply
-// on load; two_units: BN-backward sums of two units) beside the geometry in p.
+// VS_CONV_NAIVE away, and it passes the launch state they depend on (bnb: the dgrad emits BN-backward sums;
+// two_units: BN-backward sums of two units) beside the geometry in p.
 // Geometry of the halo kernel for this launch (mode = kernel MODE, dgrad: mirrored taps, flags = desc.flags),
 // or false when the implicit-GEMM kernel runs it.
 bool vs_halo_plan(const ConvP& p, int mode, int dgrad, int flags, HaloGeo* out);
@@ -538,13 +533,12 @@ struct PwGeo {
 };
 bool vs_pw_plan(const ConvP& p, int mode, int flags, bool bnb, PwGeo* out);
 int vs_pw_launch(const ConvP& p, const PwGeo& g, hipStream_t st);
-bool vs_pw_aol_ok(const PwGeo& g, int K, bool bnb);
 
 // ---- deep-pipeline kernel (conv_deep.hip): 256 x 256 x 64 tile, 8 waves, sub-buffer ring 7 phases deep ----
 struct DeepGeo {
   int tilesM, tilesN;  // 256 x 256 tiles (tilesM = rows of the batch-statistic / BN-backward partials)
   int smem;            // dynamic LDS of the launch
 };
-bool vs_deep_plan(const ConvP& p, int mode, int flags, bool aol, bool two_units, DeepGeo* out);
+bool vs_deep_plan(const ConvP& p, int mode, int flags, bool two_units, DeepGeo* out);
 int vs_deep_launch(const ConvP& p, int mode, const DeepGeo& g, hipStream_t st);
 

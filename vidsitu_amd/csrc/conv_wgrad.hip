@@ -39,10 +39,6 @@ struct WgradP {
   int xcd_order;  // 1: XCD-aware block order (default); 0: round-robin (VS_WGRAD_XCD=0, A/B)
   int dbg;        // VS_WGRAD_DBG ablations of the ring kernel (wrong results; tools only): 1 no MFMA, 2 no copies in
                   // the loop, 4 no vmcnt wait, 8 no barrier, 16 no fragment reads, 32 no table rebuild, 64 no epilogue
-  // Apply on load (pointwise ring launches): x is the producer unit's RAW convolution output and the operand is
-  // relu(x * in_scale[c] + in_shift[c]) rounded to bf16 (vs_bn_apply's bits), formed on the fragments.  NULL: off.
-  const float* in_scale;
-  const float* in_shift;
 };
 
 #define WG_OOB 0x80000000u
@@ -352,9 +348,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
 // them instead of two, i.e. three 32-position steps in flight behind `vmcnt(8)` instead of one 64-position step behind
 // `vmcnt(0)`, at 2 blocks per CU as before (whole 256-byte rows either way: halving the K depth of THIS kernel's stage
 // halves the row count, not the row length).  One barrier per 16 MFMAs per wave instead of per 32.
-template <int BM, int BN, int WM, int WN, int MODE, int NS, bool AOL = false, int ROWS = 64>
+template <int BM, int BN, int WM, int WN, int MODE, int NS, int ROWS = 64>
 __device__ __forceinline__ void conv_wgrad_ring_body(const WgradP& p, const int blk, const int nblk) {
-  static_assert(!AOL || MODE == 0, "apply on load: pointwise launches");
   static_assert(ROWS == 64, "stage depth (the half-depth variant of round 4 was measured slower and removed)");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int TM = BM / WM, TN = BN / WN;
@@ -512,14 +507,6 @@ __device__ __forceinline__ void conv_wgrad_ring_body(const WgradP& p, const int 
 #pragma unroll
     for (int b = 0; b < NR; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  // AOL: a lane's x fragment of n-tile b holds 8 positions of ONE input channel (the column it also stores)
-  float asc[NR], ash[NR];
-#pragma unroll
-  for (int b = 0; b < NR; ++b) {
-    const int col = n0 + wn * TN + b * 16 + li;
-    asc[b] = (AOL && col < p.Kp) ? p.in_scale[col] : 0.f;
-    ash[b] = (AOL && col < p.Kp) ? p.in_shift[col] : 0.f;
-  }
   auto compute = [&](int stage) __attribute__((always_inline)) {
     const char* A = smem + stage * STAGE;
     const char* B = A + IMG;
@@ -544,7 +531,6 @@ __device__ __forceinline__ void conv_wgrad_ring_body(const WgradP& p, const int 
         const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)ptr);
         const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(ptr + 128));
         bfr[b] = __builtin_bit_cast(bf16x8, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-        if (AOL) bfr[b] = aol_frag_n(bfr[b], asc[b], ash[b]);
       }
 #pragma unroll
       for (int a = 0; a < MR; ++a)
@@ -591,9 +577,9 @@ __device__ __forceinline__ void conv_wgrad_ring_body(const WgradP& p, const int 
     }
 }
 
-template <int BM, int BN, int WM, int WN, int MODE, int NS, bool AOL = false, int ROWS = 64>
+template <int BM, int BN, int WM, int WN, int MODE, int NS, int ROWS = 64>
 __global__ __launch_bounds__(256) void conv_wgrad_ring_kernel(WgradP p) {
-  conv_wgrad_ring_body<BM, BN, WM, WN, MODE, NS, AOL, ROWS>(p, blockIdx.x, gridDim.x);
+  conv_wgrad_ring_body<BM, BN, WM, WN, MODE, NS, ROWS>(p, blockIdx.x, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1271,18 +1257,6 @@ static int wg_launch(const WgradP& p, int mode, int ring, hipStream_t st) {
     if constexpr (BM == 128 && BN == 128) {
       if (ring == 2 && pair_take_wgrad(p, grid, smem, mode, st)) return VS_OK;
     }
-    if (p.in_scale) {  // apply on load: wgrad_aol_ok admitted only (128-row tile, 2-stage ring, pointwise)
-      if constexpr (BM == 128) {
-        static std::once_flag aattr;
-        std::call_once(aattr, [] {
-          (void)hipFuncSetAttribute((const void*)conv_wgrad_ring_kernel<BM, BN, WM, WN, 0, 2, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        });
-        hipLaunchKernelGGL((conv_wgrad_ring_kernel<BM, BN, WM, WN, 0, 2, true>), dim3(grid), dim3(256), smem, st, p);
-        VS_CHECK_LAUNCH();
-        return VS_OK;
-      }
-    }
     if (ring == 2 && mode == 0)
       hipLaunchKernelGGL((conv_wgrad_ring_kernel<BM, BN, WM, WN, 0, 2>), dim3(grid), dim3(256), smem, st, p);
     else if (ring == 2)
@@ -1303,21 +1277,10 @@ static int wg_launch(const WgradP& p, int mode, int ring, hipStream_t st) {
   return VS_OK;
 }
 
-// the launch apply on load is built for: pointwise, unit stride, the 128-row tiles on the two-stage ring
-static bool wgrad_aol_plan_ok(const vs_conv_desc* d) {
-  const bool dense = (d->kT * d->kH * d->kW == 1) && d->sT == 1 && d->sH == 1 && d->sW == 1 &&
-                     d->pT == 0 && d->pH == 0 && d->pW == 0;
-  if (!dense || ((d->flags >> 16) & 7) || ((d->flags >> 8) & 0xf)) return false;
-  const WgCfg c = wg_pick(d);
-  return c.bm == 128 && (c.bn == 128 || c.bn == 64);
-}
-
 // WgradP of one weight gradient from its descriptor and plan (tensor pointers, extents, tile counts, split)
 static int wg_fill_params(WgradP& p, const void* dy, const void* x, float* out, const vs_conv_desc* d, const WgCfg& c) {
   p.dy = (const uint16_t*)dy;
   p.x = (const uint16_t*)x;
-  p.in_scale = nullptr;
-  p.in_shift = nullptr;
   p.out = out;
   p.P = d->N * d->To * d->Ho * d->Wo;
   p.Cout = d->Cout;
@@ -1609,8 +1572,7 @@ extern "C" int vs_conv_wgrad_group(const vs_wgrad_item* items, int n, void* work
 }
 
 static int wgrad_impl(const void* dy, const void* x, float* dw, const vs_conv_desc* d, void* workspace,
-                      size_t ws_bytes, void* stream, bool reduce_now, int* splits_out,
-                      const float* in_scale = nullptr, const float* in_shift = nullptr) {
+                      size_t ws_bytes, void* stream, bool reduce_now, int* splits_out) {
   VS_CHECK_ARG(d && dy && x && dw, "null argument");
   VS_CHECK_ARG(d->Cin % 8 == 0 && d->Cout % 8 == 0, "Cin and Cout must be multiples of 8");
   VS_CHECK_ARG(d->x_ld % 8 == 0 && d->y_ld % 8 == 0, "row pitches must be multiples of 8");
@@ -1622,17 +1584,11 @@ static int wgrad_impl(const void* dy, const void* x, float* dw, const vs_conv_de
     return VS_ERR_WORKSPACE;
   }
   if (g_pending.have && ((const void*)g_pending.r.slabs == workspace || g_pending.r.dw == dw)) pending_flush();
-  if (in_scale && !wgrad_aol_plan_ok(d)) {
-    vs_set_error("vs_conv_wgrad_aol: apply on load is not built for this weight gradient (ask vs_conv_wgrad_aol_ok)");
-    return VS_ERR_UNSUPPORTED;
-  }
   WgradP p;
   {
     const int rc = wg_fill_params(p, dy, x, c.S > 1 ? (float*)workspace : dw, d, c);
     if (rc) return rc;
   }
-  p.in_scale = in_scale;
-  p.in_shift = in_shift;
   {
     static const int xo = [] { const char* e = getenv("VS_WGRAD_XCD"); return e ? atoi(e) : 1; }();
     // measured per layer (batch 8): a win up to ~16 output tiles (s3.b 43.5 -> 35.4 us, s4.c 22.1 -> 19.7,
@@ -1663,10 +1619,6 @@ static int wgrad_impl(const void* dy, const void* x, float* dw, const vs_conv_de
       (void)hipFuncSetAttribute((const void*)conv_wgrad_deep_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
     static const int stag = [] { const char* e = getenv("VS_WGRAD_DEEP_STAG"); return e ? atoi(e) : 1; }();  // +2.7 % at 32 clips, neutral at 8
-    if (in_scale) {
-      vs_set_error("vs_conv_wgrad_aol: not built for the deep-pipeline plan");
-      return VS_ERR_UNSUPPORTED;
-    }
     const size_t smem = (size_t)WGD_NU * WGD_UNIT + 2 * WGD_TAB * sizeof(int2);
     const int grid = p.tilesM * p.tilesN * p.S;
     if (stag && mode == 0) hipLaunchKernelGGL((conv_wgrad_deep_kernel<0, true>), dim3(grid), dim3(512), smem, st, p);
@@ -1702,16 +1654,6 @@ extern "C" int vs_conv_wgrad(const void* dy, const void* x, float* dw, const vs_
                              void* workspace,
                              size_t ws_bytes, void* stream) {
   return wgrad_impl(dy, x, dw, d, workspace, ws_bytes, stream, true, nullptr);
-}
-
-// dW of a 1x1x1 convolution whose input is relu(x * in_scale[c] + in_shift[c]) with x the producer unit's raw output
-// (see vs_conv_fwd_aol): the operand vs_bn_apply would have stored, formed on the fragments.  _ok: 1 where built.
-extern "C" int vs_conv_wgrad_aol_ok(const vs_conv_desc* d) { return (d && wgrad_aol_plan_ok(d)) ? 1 : 0; }
-
-extern "C" int vs_conv_wgrad_aol(const void* dy, const void* x, float* dw, const vs_conv_desc* d, const float* in_scale,
-                                 const float* in_shift, void* workspace, size_t ws_bytes, void* stream) {
-  VS_CHECK_ARG(in_scale && in_shift, "null constants");
-  return wgrad_impl(dy, x, dw, d, workspace, ws_bytes, stream, true, nullptr, in_scale, in_shift);
 }
 
 extern "C" int vs_conv_wgrad_partial(const void* dy, const void* x, float* dw, const vs_conv_desc* d, void* slabs,

@@ -265,7 +265,7 @@ class TrainStep:
 
         main = torch.cuda.current_stream()
         cands = [getattr(self.arena, "_tr_stream", None), self._adam_stream]
-        cands += list(_trunk.VideoTrunk._side_streams.values()) + list(_trunk.VideoTrunk._reduce_streams.values())
+        cands += list(_trunk.VideoTrunk._side_streams.values())
         cands += [lane[1] for lane in _trunk._WgradLanes.lanes.values()]
         for st in cands:
             if st is None or st.cuda_stream == main.cuda_stream:

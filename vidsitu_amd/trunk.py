@@ -151,89 +151,65 @@ class _WgradLanes:
     joining only at the end of a stage 19.1 ms, joining one unit later 17.7 ms (wgrad then competes
     with the BN passes for bandwidth), lanes for the fast pathway as well 18.8 ms; a lane forked from
     AND joined back into the trunk's (already forked) side stream makes hipStreamEndCapture
-    segfault on ROCm 7.2, so launches issued from that stream stay inline.  VS_WGRAD_LANES=0: off."""
+    segfault on ROCm 7.2, so launches issued from that stream stay inline.  Also measured and removed (docs/round2.md):
+    letting the lane lag a unit behind, or its slab reduce run behind the event -- any lane work still running when
+    the issuing stream starts the next unit's BN kernels costs ~25 us per unit under replay (16.1-16.3 ms vs 13.4-13.5).
+    VS_WGRAD_LANES=0: off."""
 
     enabled = os.environ.get("VS_WGRAD_LANES", "1") != "0"
-    # units the lane may lag behind the issuing stream before that stream waits for it (0: joined right after
-    # the unit's dgrad).  VS_WGRAD_LAG: A/B knob.
-    lag = int(os.environ.get("VS_WGRAD_LAG", "0"))
     # device index -> [issuing stream, lane stream, queue of (event, keepalive) per launched unit].  Lane streams
     # are created once (never inside a hipGraph capture, where creating a stream is an unsafe call).
     lanes = {}
-
-    # A fork + join pair costs ~17 us in a replayed hipGraph on this system (tools/graph_edge_cost.py): a weight
-    # gradient only goes to the lane when its convolution is at least this large (GFLOP of the unit's GEMM);
-    # smaller ones run inline in front of the dgrad.  VS_WGRAD_LANE_MIN_GFLOP: sweep knob.
-    min_gflop = float(os.environ.get("VS_WGRAD_LANE_MIN_GFLOP", "0"))
     defer_active = False  # inside VideoTrunk._backward_segment with ops.REDUCE_MERGE (see there)
 
     @classmethod
-    def run(cls, fn, *keep, gflop=None):
-        """fn runs on the lane; if it returns a callable (the slab reduce of ops.conv_wgrad_split) that runs on the
-        lane too, but BEHIND the event the issuing stream waits for: the reduce reads no operand of the unit, so the
-        issuing stream goes on as soon as the wgrad kernel itself is done (~7 us per unit off its critical path)."""
-        if not cls.enabled or not keep[0].is_cuda or (gflop is not None and gflop < cls.min_gflop):
-            tail = fn()
-            return tail() if callable(tail) else None
+    def run(cls, fn, *keep, inline=False):
+        """fn runs on the lane -- or, with `inline` (the unit's paired launch records it), on the issuing stream."""
+        if inline or not cls.enabled or not keep[0].is_cuda:
+            fn()
+            return
         main = torch.cuda.current_stream()
         dev = main.device.index
         side = VideoTrunk._side_streams.get(dev)
         if side is not None and side.cuda_stream == main.cuda_stream:
-            tail = fn()  # issued from the fast pathway's stream: no nested fork
-            return tail() if callable(tail) else None
+            fn()  # issued from the fast pathway's stream: no nested fork
+            return
         lane = cls.lanes.get(dev)
         if lane is None:
-            lane = cls.lanes[dev] = [main, torch.cuda.Stream(device=main.device), [], False]
+            lane = cls.lanes[dev] = [main, torch.cuda.Stream(device=main.device), []]
         if lane[2] and lane[0].cuda_stream != main.cuda_stream:  # never leave a lane un-joined
-            cls._drain(lane, 0)
+            cls._drain(lane)
         lane[0] = main
         lane[1].wait_stream(main)
         deferring = _WgradLanes.defer_active
         if deferring:
             ops.wgrad_reduce_defer(2)  # the lane's completion event must cover the slab reduce: launched as usual
         with torch.cuda.stream(lane[1]):
-            tail = fn()
+            fn()
             ev = torch.cuda.Event()
             ev.record(lane[1])
-            if callable(tail):
-                tail()
-                lane[3] = True  # work behind the last event: a full join waits for the stream, not the event
         if deferring:
             ops.wgrad_reduce_defer(1)
         lane[2].append((ev, keep))
 
     @staticmethod
-    def _drain(lane, lag):
-        while len(lane[2]) > lag:
+    def _drain(lane):
+        while lane[2]:
             ev, _ = lane[2].pop(0)
             lane[0].wait_event(ev)
 
     @classmethod
-    def join_unit(cls):
-        """After a unit's dgrad: wait for the weight gradients launched more than `lag` units ago."""
-        for lane in cls.lanes.values():
-            cls._drain(lane, cls.lag)
-
-    @classmethod
     def join_all(cls):
+        """The issuing streams wait for every weight gradient still on a lane (after each unit's dgrad, and wherever
+        streams join)."""
         for lane in cls.lanes.values():
-            cls._drain(lane, 0)
-            if lane[3]:
-                lane[0].wait_stream(lane[1])
-                lane[3] = False
+            cls._drain(lane)
 
 
 class _Unit:
     """conv -> BN (-> +residual) (-> ReLU) executed on the HIP kernels."""
 
     trace = None  # debugging: set to a list to record (conv, y, z, mean, invstd) per unit
-    wgrad_batch = None  # the running trunk backward's ops.WgradBatch (set by VideoTrunk._backward_segment)
-    # VS_WGRAD_TAIL=1: the slab reduce of a weight gradient runs behind the event its unit's stream waits for (the
-    # reduce reads no operand of the unit).  Measured: 16.3 ms vs 13.5 ms per step under hipGraph replay -- like the
-    # lagged join (`_WgradLanes.lag`), ANY lane work that is still running when the issuing stream starts the next
-    # unit's BN kernels costs ~25 us per unit; the replay then takes as long as the one-stream graph (17.0 ms).
-    # Eager (host-bound, 24-26 ms) does not show it.  Off.
-    split_wgrad_reduce = os.environ.get("VS_WGRAD_TAIL", "0") == "1"
     # BN-backward sums of the a / b units of a bottleneck emitted by the consuming convolution's dgrad
     # epilogue (vs_conv_dgrad_bnstats) instead of a reduce pass of their own; VS_FUSE_BN_SUMS=0 = A/B switch
     fuse_bn_sums = os.environ.get("VS_FUSE_BN_SUMS", "1") != "0"
@@ -275,14 +251,10 @@ class _Unit:
             _Unit.calib[conv] = mu
 
     @staticmethod
-    def fwd(conv, bn, x, relu, residual=None, out=None, train=False, saved=None, pool=False, no_apply=False,
-            x_affine=None, defer_apply=False, residual_affine=None):
+    def fwd(conv, bn, x, relu, residual=None, out=None, train=False, saved=None, pool=False, defer_apply=False,
+            residual_affine=None):
         """pool (train mode, the stems): the unit's output goes through the [1,3,3] max-pool and nowhere else --
         BN + ReLU + pool run as one pass, the record gets the argmax bytes (`pool_idx`) and no `z`.
-        Apply on load (train mode, `ResBlock.aol`): `no_apply` -- the unit stops behind its finalize and returns
-        (y, (scale, shift)); its consumer is called with `x` = that raw y and `x_affine` = the constants and forms
-        relu(y * scale + shift) on its operand fragments (ops.conv_fwd_aol / conv_wgrad_aol): the activation is never
-        stored.
         Shortcut apply in the block's last pass (train mode, `ResBlock.fuse_sc_apply`): the shortcut unit is called with
         `defer_apply` -- it stops behind its finalize and returns (y, (scale, shift)) -- and the c unit with
         `residual_affine` = that pair: its apply pass forms the shortcut's normalised output on the fly (ops.bn_apply2,
@@ -320,8 +292,6 @@ class _Unit:
         if conv.is_stem:
             y, partials = ops.stem_conv_fwd(x[0], conv.w_stem, conv.cout, conv.k[0], stats=True)
             x = x[0]  # the stem wgrad kernel reads the same C=4 packed input
-        elif x_affine is not None:
-            y, partials = ops.conv_fwd_aol(x, conv.w_bf16, x_affine[0], x_affine[1], stats=True)
         else:
             y, partials = ops.conv_fwd(x, conv.w_bf16, conv.k, conv.s, conv.p, stats=True)
         scale, shift, mean, invstd = ops.bn_finalize(
@@ -333,14 +303,9 @@ class _Unit:
             with torch.no_grad():
                 bn.running_mean.add_(conv.bias.detach() * bn.momentum)
         if defer_apply:  # a ReLU-less unit whose output is formed by its only reader (the block's last apply pass)
-            assert not relu and residual is None and not pool and x_affine is None
+            assert not relu and residual is None and not pool
             saved.append(dict(conv=conv, bn=bn, x=x, y=y, z=None, zbits=None, mean=mean, invstd=invstd,
-                              relu=False, has_res=False, x_affine=None))
-            return y, (scale, shift)
-        if no_apply:  # the consumer applies scale / shift / ReLU on load; backward recomputes the mask from y
-            assert relu and residual is None and not pool
-            saved.append(dict(conv=conv, bn=bn, x=x, y=y, z=None, zbits=None, mean=mean, invstd=invstd,
-                              relu=True, has_res=False, aol=True, x_affine=x_affine))
+                              relu=False, has_res=False))
             return y, (scale, shift)
         # a unit with a residual input cannot recompute its ReLU mask from y alone: keep it as bits
         if pool and not ops.bn_apply_maxpool_ok(y):
@@ -355,7 +320,7 @@ class _Unit:
             assert relu and residual is None
             z, zbits = ops.bn_apply2(y, scale, shift, y2, sc2, sh2, out=out, want_bits=True)
             saved.append(dict(conv=conv, bn=bn, x=x, y=y, z=z, zbits=zbits, mean=mean, invstd=invstd,
-                              relu=True, has_res=True, x_affine=x_affine))
+                              relu=True, has_res=True))
             return z
         want_bits = relu and residual is not None and y.shape[1] % 8 == 0 and \
             ((y.shape[1] // 8) & (y.shape[1] // 8 - 1)) == 0
@@ -366,7 +331,7 @@ class _Unit:
         if _Unit.trace is not None:
             _Unit.trace.append((conv, y.float().cpu(), z.float().cpu(), mean.cpu(), invstd.cpu()))
         saved.append(dict(conv=conv, bn=bn, x=x, y=y, z=z, zbits=zbits, mean=mean, invstd=invstd,
-                          relu=relu, has_res=residual is not None, x_affine=x_affine))
+                          relu=relu, has_res=residual is not None))
         return z
 
     @staticmethod
@@ -387,120 +352,87 @@ class _Unit:
         conv, bn = rec["conv"], rec["bn"]
         if dy_ready is not None:
             assert not want_dres
-            x = rec["x"]
-            pair = (_Unit.pair_launch and need_dx and not conv.is_stem and conv.cin_pad == conv.cin and dy_ready.is_cuda
-                    and _Unit.wgrad_batch is None and not _Unit.split_wgrad_reduce and wgrad_sink is None)
-            pair_ctx = ops.conv_pair() if pair else contextlib.nullcontext()
-            pair_ctx.__enter__()
-            try:
-                dx = _Unit._bwd_convs(conv, dy_ready, x, need_dx, producer, dx_residual, dx_residual_bits, inplace, pair,
-                                      rec.get("x_affine"), wgrad_sink)
-            finally:
-                pair_ctx.__exit__(None, None, None)
-            _WgradLanes.join_unit()
-            return dx, None
-        relu = rec["relu"] and not masked
-        if bn.weight.grad is None:
-            bn.weight.grad = torch.zeros_like(bn.weight)
-        if bn.bias.grad is None:
-            bn.bias.grad = torch.zeros_like(bn.bias)
-        # without a residual input the ReLU mask is recomputed from y (z is not read)
-        zbits = rec.get("zbits") if relu else None
-        zmask = rec["z"] if (relu and rec["has_res"] and zbits is None) else None
-        if dz_bits is not None:
-            assert not rec["relu"], "dz_bits belongs to a unit without a ReLU of its own"
-            relu, zbits, zmask = True, dz_bits, None
-        pidx = rec.get("pool_idx")  # a stem unit run with pool=True: dz is the POOLED tensor's gradient
-        dy, dres, _, _ = ops.bn_bwd(
-            None if pidx is not None else dz, zmask, rec["y"], rec["mean"], rec["invstd"], bn.weight, relu, want_dres,
-            dgamma=bn.weight.grad, dbeta=bn.bias.grad, beta=bn.bias, zbits=zbits,
-            partial=rec.pop("bwd_partial", None), pool_src=(dz, pidx) if pidx is not None else None)
-        x = rec["x"]
-        if conv.bias is not None:  # analytically zero behind a train-mode BN
-            if conv.bias.grad is None:
-                conv.bias.grad = torch.zeros_like(conv.bias)
-            else:
-                conv.bias.grad.zero_()
-        # one launch for the unit's two gradients where both kernels allow it (`pair_launch`): the weight gradient is
-        # then issued inline (recorded, like the data gradient below) instead of on the lane
-        pair = (_Unit.pair_launch and need_dx and not conv.is_stem and conv.cin_pad == conv.cin and dy.is_cuda
-                and _Unit.wgrad_batch is None and not _Unit.split_wgrad_reduce and wgrad_sink is None)
-        pair_ctx = ops.conv_pair() if pair else contextlib.nullcontext()
-        pair_ctx.__enter__()
-        try:
-            dx = _Unit._bwd_convs(conv, dy, x, need_dx, producer, dx_residual, dx_residual_bits, inplace, pair,
-                                  rec.get("x_affine"), wgrad_sink)
-        finally:
-            pair_ctx.__exit__(None, None, None)
-        _WgradLanes.join_unit()  # wgrad || dgrad of this unit (and, with a lag, of the next units)
+            dy, dres = dy_ready, None
+        else:
+            relu = rec["relu"] and not masked
+            if bn.weight.grad is None:
+                bn.weight.grad = torch.zeros_like(bn.weight)
+            if bn.bias.grad is None:
+                bn.bias.grad = torch.zeros_like(bn.bias)
+            # without a residual input the ReLU mask is recomputed from y (z is not read)
+            zbits = rec.get("zbits") if relu else None
+            zmask = rec["z"] if (relu and rec["has_res"] and zbits is None) else None
+            if dz_bits is not None:
+                assert not rec["relu"], "dz_bits belongs to a unit without a ReLU of its own"
+                relu, zbits, zmask = True, dz_bits, None
+            pidx = rec.get("pool_idx")  # a stem unit run with pool=True: dz is the POOLED tensor's gradient
+            dy, dres, _, _ = ops.bn_bwd(
+                None if pidx is not None else dz, zmask, rec["y"], rec["mean"], rec["invstd"], bn.weight, relu, want_dres,
+                dgamma=bn.weight.grad, dbeta=bn.bias.grad, beta=bn.bias, zbits=zbits,
+                partial=rec.pop("bwd_partial", None), pool_src=(dz, pidx) if pidx is not None else None)
+            if conv.bias is not None:  # analytically zero behind a train-mode BN
+                if conv.bias.grad is None:
+                    conv.bias.grad = torch.zeros_like(conv.bias)
+                else:
+                    conv.bias.grad.zero_()
+        dx = _Unit._bwd_convs(conv, dy, rec["x"], need_dx, producer, dx_residual, dx_residual_bits, inplace, wgrad_sink)
+        _WgradLanes.join_all()  # wgrad || dgrad of this unit
         return dx, dres
 
     @staticmethod
-    def _bwd_convs(conv, dy, x, need_dx, producer, dx_residual, dx_residual_bits, inplace, pair, x_affine=None,
-                   wgrad_sink=None):
-        """The unit's weight gradient (side lane, or inline when `pair`) and data gradient.  x_affine: x is the
-        producer's raw output, the weight gradient applies its BN + ReLU on load.  wgrad_sink: see `bwd`."""
-        if wgrad_sink is not None:
-            if conv.weight.grad is None:
-                conv.weight.grad = torch.empty_like(conv.weight)
-            wgrad_sink.append((dy, x, conv))
-        elif conv.is_stem:
-            _WgradLanes.run(lambda: _set_grad(conv.weight, ops.stem_conv_wgrad(dy, x, conv.k[0])) and None, dy, x)
-        elif conv.cin_pad == conv.cin:
-            if conv.weight.grad is None:
-                conv.weight.grad = torch.empty_like(conv.weight)
-            # gradients that live in a ParamArena keep their address: their position-split partials go to the
-            # trunk's WgradBatch and are summed by one launch per backward segment (VideoTrunk._flush_wgrads)
-            batch = _Unit.wgrad_batch if getattr(conv.weight, "_vs_direct_grad", False) else None
-            gf = 2e-9 * dy.numel() * conv.cin * conv.k[0] * conv.k[1] * conv.k[2]  # the unit's GEMM, GFLOP
-            if pair:
-                gf = -1.0  # inline
-            if x_affine is not None:
-                _WgradLanes.run(lambda: (ops.conv_wgrad_aol(dy, x, x_affine[0], x_affine[1], out=conv.weight.grad),
-                                         None)[1], dy, x, gflop=gf)
-            elif batch is not None:
-                _WgradLanes.run(lambda: (ops.conv_wgrad(dy, x, conv.k, conv.s, conv.p, out=conv.weight.grad,
-                                                        batch=batch), None)[1], dy, x, gflop=gf)
-            elif _Unit.split_wgrad_reduce:
-                _WgradLanes.run(lambda: ops.conv_wgrad_split(dy, x, conv.k, conv.s, conv.p, conv.weight.grad), dy, x,
-                                gflop=gf)
+    def _bwd_convs(conv, dy, x, need_dx, producer, dx_residual, dx_residual_bits, inplace, wgrad_sink):
+        """The unit's weight gradient (handed to the block's grouped launch, on the side lane, or inline when paired)
+        and data gradient.  wgrad_sink: see `bwd`."""
+        # one launch for the unit's two gradients where both kernels allow it (`pair_launch`): the weight gradient is
+        # then issued inline (recorded, like the data gradient below) instead of on the lane
+        pair = (_Unit.pair_launch and need_dx and not conv.is_stem and conv.cin_pad == conv.cin and dy.is_cuda
+                and wgrad_sink is None)
+        with ops.conv_pair() if pair else contextlib.nullcontext():
+            if wgrad_sink is not None:
+                if conv.weight.grad is None:
+                    conv.weight.grad = torch.empty_like(conv.weight)
+                wgrad_sink.append((dy, x, conv))
+            elif conv.is_stem:
+                _WgradLanes.run(lambda: _set_grad(conv.weight, ops.stem_conv_wgrad(dy, x, conv.k[0])), dy, x)
+            elif conv.cin_pad == conv.cin:
+                if conv.weight.grad is None:
+                    conv.weight.grad = torch.empty_like(conv.weight)
+                _WgradLanes.run(lambda: ops.conv_wgrad(dy, x, conv.k, conv.s, conv.p, out=conv.weight.grad), dy, x,
+                                inline=pair)
             else:
-                _WgradLanes.run(lambda: (ops.conv_wgrad(dy, x, conv.k, conv.s, conv.p, out=conv.weight.grad),
-                                         None)[1], dy, x, gflop=gf)
-        else:
-            def legacy():
-                dwp = ops.conv_wgrad(dy, x, conv.k, conv.s, conv.p)
-                _set_grad(conv.weight, dwp[:, : conv.cin])
-            _WgradLanes.run(legacy, dy, x)
-        dx = None
-        if need_dx:
-            # the producer's complete dz is this dx when its output feeds this convolution and -- with
-            # dx_residual -- the branch whose gradient arrives as that residual, and nothing else
-            fuse = (_Unit.fuse_bn_sums and producer is not None and "conv" in producer and producer["relu"]
-                    and (producer["y"] is x if producer.get("aol") else producer["z"] is x))
-            if fuse and dx_residual is None:
-                fuse = not producer["has_res"] and producer.get("zbits") is None
-            elif fuse:
-                fuse = producer.get("zbits") is not None
-            part = None
-            if fuse:
-                pbn = producer["bn"]
-                # the producer's block may have a shortcut unit: it receives the same masked gradient (one more
-                # sum(g * xhat) from the same epilogue instead of a reduce pass of its own over dz and its y)
-                sc = producer.get("sc_rec") if (_Unit.fuse_sc_sums and dx_residual is not None) else None
-                res = ops.conv_dgrad(dy, conv.wt(), tuple(x.shape), conv.k, conv.s, conv.p,
-                                     residual=dx_residual, residual_bits=dx_residual_bits,
-                                     bn_stats=(producer["y"], producer["mean"], producer["invstd"],
-                                               pbn.weight, pbn.bias, producer.get("zbits")),
-                                     bn_stats2=(sc["y"], sc["mean"], sc["invstd"]) if sc is not None else None)
-                dx, part = res[0], res[1]
-                if part is not None:
-                    producer["bwd_partial"] = part
-                    if sc is not None and res[2] is not None:
-                        sc["bwd_partial"] = res[2]
-            else:
-                dx = ops.conv_dgrad(dy, conv.wt(), tuple(x.shape), conv.k, conv.s, conv.p,
-                                    residual=dx_residual, residual_bits=dx_residual_bits, inplace=inplace)
+                def legacy():
+                    dwp = ops.conv_wgrad(dy, x, conv.k, conv.s, conv.p)
+                    _set_grad(conv.weight, dwp[:, : conv.cin])
+                _WgradLanes.run(legacy, dy, x)
+            dx = None
+            if need_dx:
+                # the producer's complete dz is this dx when its output feeds this convolution and -- with
+                # dx_residual -- the branch whose gradient arrives as that residual, and nothing else
+                fuse = (_Unit.fuse_bn_sums and producer is not None and "conv" in producer and producer["relu"]
+                        and producer["z"] is x)
+                if fuse and dx_residual is None:
+                    fuse = not producer["has_res"] and producer.get("zbits") is None
+                elif fuse:
+                    fuse = producer.get("zbits") is not None
+                part = None
+                if fuse:
+                    pbn = producer["bn"]
+                    # the producer's block may have a shortcut unit: it receives the same masked gradient (one more
+                    # sum(g * xhat) from the same epilogue instead of a reduce pass of its own over dz and its y)
+                    sc = producer.get("sc_rec") if (_Unit.fuse_sc_sums and dx_residual is not None) else None
+                    res = ops.conv_dgrad(dy, conv.wt(), tuple(x.shape), conv.k, conv.s, conv.p,
+                                         residual=dx_residual, residual_bits=dx_residual_bits,
+                                         bn_stats=(producer["y"], producer["mean"], producer["invstd"],
+                                                   pbn.weight, pbn.bias, producer.get("zbits")),
+                                         bn_stats2=(sc["y"], sc["mean"], sc["invstd"]) if sc is not None else None)
+                    dx, part = res[0], res[1]
+                    if part is not None:
+                        producer["bwd_partial"] = part
+                        if sc is not None and res[2] is not None:
+                            sc["bwd_partial"] = res[2]
+                else:
+                    dx = ops.conv_dgrad(dy, conv.wt(), tuple(x.shape), conv.k, conv.s, conv.p,
+                                        residual=dx_residual, residual_bits=dx_residual_bits, inplace=inplace)
         return dx
 
 
@@ -587,24 +519,6 @@ class ResBlock(nn.Module):
     # (ops.conv_fwd_bc: the inner tensor stays in LDS).  VS_EVAL_FUSE_BC=0: two launches (A/B switch).
     fuse_bc = os.environ.get("VS_EVAL_FUSE_BC", "1") != "0"
 
-    # Train: the b -> c edge without the stored activation (apply on load, `_Unit.fwd(no_apply / x_affine)`) where the
-    # c unit's forward and weight-gradient plans have the fragment transform (slow pathway).  VS_TRAIN_AOL=0 / 1.
-    aol = os.environ.get("VS_TRAIN_AOL", "0") == "1"
-
-    def _aol_ok(self, a, saved):
-        b2 = self.branch2
-        if (not ResBlock.aol or saved is None or not a.is_cuda or _Unit.trace is not None or _Unit.wgrad_batch is not None
-                or _Unit.split_wgrad_reduce or b2.b.bias is not None or b2.c.bias is not None
-                or b2.c.cin_pad != b2.c.cin):
-            return False
-        key = ("aol",) + tuple(a.shape)
-        hit = self.__dict__.setdefault("_bc_ok", {}).get(key)
-        if hit is None:
-            yb_shape = ops.conv_out_shape(a.shape, b2.b.cout, b2.b.k, b2.b.s, b2.b.p)
-            probe = ops.new_act(*yb_shape, device=a.device)  # (shape / pitch carrier for the plan query)
-            hit = self._bc_ok[key] = ops.conv_aol_ok(probe, b2.c.cout)
-        return hit
-
     def _bc_fusable(self, a):
         b2 = self.branch2
         if (not ResBlock.fuse_bc or _Unit.split_weights or ResBlock.residual_fp32 or not a.is_cuda
@@ -633,12 +547,6 @@ class ResBlock(nn.Module):
             b = _Unit.fwd(b2.b, b2.b_bn, a, True, train=True, saved=saved)
             z = _Unit.fwd(b2.c, b2.c_bn, b, True, out=out, train=True, saved=saved, residual_affine=sc_aff)
             if saved is not None and len(saved) >= 4:
-                saved[-1]["sc_rec"] = saved[-4]
-            return z
-        if train and self._aol_ok(a, saved):
-            yb, aff = _Unit.fwd(b2.b, b2.b_bn, a, True, train=True, saved=saved, no_apply=True)
-            z = _Unit.fwd(b2.c, b2.c_bn, yb, True, residual=sc, out=out, train=True, saved=saved, x_affine=aff)
-            if self.has_sc and saved is not None and len(saved) >= 4:
                 saved[-1]["sc_rec"] = saved[-4]
             return z
         if not train and self._bc_fusable(a):
@@ -704,8 +612,7 @@ class ResBlock(nn.Module):
     group_min_channels = int(os.environ.get("VS_WGRAD_GROUP_MINC", "128"))  # narrower blocks: neutral (64, 32) or slower (16, 8) in the step
 
     def _wgrad_grouped(self, rc, rb, ra, rsc, dout):
-        if (not ResBlock.group_wgrads or not dout.is_cuda or _Unit.wgrad_batch is not None or _Unit.split_wgrad_reduce
-                or ResBlock.aol):
+        if not ResBlock.group_wgrads or not dout.is_cuda:
             return False
         recs = [r for r in (rc, rb, ra, rsc) if r is not None]
         key = ("wgg",) + tuple(tuple(r["y"].shape) for r in recs)
@@ -715,7 +622,7 @@ class ResBlock(nn.Module):
             items = []
             for r in recs:
                 c, y, x = r["conv"], r["y"], r["x"]
-                if (c.is_stem or c.cin_pad != c.cin or c.bias is not None or r.get("x_affine") is not None
+                if (c.is_stem or c.cin_pad != c.cin or c.bias is not None
                         or c.cout < ResBlock.group_min_channels or not isinstance(x, torch.Tensor)
                         or not getattr(c.weight, "_vs_direct_grad", True)):
                     hit = False
@@ -759,19 +666,14 @@ class ResBlock(nn.Module):
         da, _ = _Unit.bwd(rb, db, producer=ra, wgrad_sink=sink)
         if self.has_sc:
             rsc = saved.pop()
-            if ResBlock.accumulate_shortcut:
-                # conv a's (unit-stride) data gradient first; the shortcut's dgrad then accumulates into it in
-                # place -- a strided shortcut touches only the positions its stride reaches, instead of writing
-                # a block-input-sized tensor that is 3/4 zeros and re-reading it as a residual
-                dxa, _ = _Unit.bwd(ra, da, wgrad_sink=sink)
-                if cbits is not None:
-                    dx, _ = _Unit.bwd(rsc, dout, dz_bits=cbits, dx_residual=dxa, inplace=True, dy_ready=dy_sc, wgrad_sink=sink)
-                else:
-                    dx, _ = _Unit.bwd(rsc, g, masked=True, dx_residual=dxa, inplace=True, wgrad_sink=sink)
+            # conv a's (unit-stride) data gradient first; the shortcut's dgrad then accumulates into it in
+            # place -- a strided shortcut touches only the positions its stride reaches, instead of writing
+            # a block-input-sized tensor that is 3/4 zeros and re-reading it as a residual
+            dxa, _ = _Unit.bwd(ra, da, wgrad_sink=sink)
+            if cbits is not None:
+                dx, _ = _Unit.bwd(rsc, dout, dz_bits=cbits, dx_residual=dxa, inplace=True, dy_ready=dy_sc, wgrad_sink=sink)
             else:
-                dx1, _ = (_Unit.bwd(rsc, dout, dz_bits=cbits, dy_ready=dy_sc, wgrad_sink=sink) if cbits is not None
-                          else _Unit.bwd(rsc, g, masked=True, wgrad_sink=sink))
-                dx, _ = _Unit.bwd(ra, da, dx_residual=dx1, wgrad_sink=sink)
+                dx, _ = _Unit.bwd(rsc, g, masked=True, dx_residual=dxa, inplace=True, wgrad_sink=sink)
         elif cbits is not None:
             dx, _ = _Unit.bwd(ra, da, dx_residual=dout, dx_residual_bits=cbits,
                               producer=saved[-1] if (chain and saved) else None, wgrad_sink=sink)
@@ -784,9 +686,6 @@ class ResBlock(nn.Module):
     fuse_sc_bwd = os.environ.get("VS_FUSE_SC_BWD", "1") != "0"
     # Train: the shortcut unit's BN apply inside the c unit's apply pass (ops.bn_apply2).  VS_FUSE_SC_APPLY=0: two passes.
     fuse_sc_apply = os.environ.get("VS_FUSE_SC_APPLY", "1") != "0"
-
-    # A/B switch (VS_ACC_SHORTCUT=0: the round-1 data flow of the shortcut's gradient)
-    accumulate_shortcut = os.environ.get("VS_ACC_SHORTCUT", "1") != "0"
 
 
 class Nonlocal(nn.Module):
@@ -1165,7 +1064,6 @@ class VideoTrunk(nn.Module):
         # (eval_graph.EvalGraph records it at capture and refuses to replay under another)
         self.eval_version = 0
         self.debug_taps = None  # set to a dict to record the activations after every stage
-        self._wgrad_batch, self._reduce_pending = None, False
         self.num_classes = int(getattr(cfg.MODEL, "NUM_CLASSES", 400))
 
     def reference_only_params(self):
@@ -1464,57 +1362,20 @@ class VideoTrunk(nn.Module):
                  "rest": ["s1", "s1_fuse", "s2", "s2_fuse", "s3", "s3_fuse"]}[seg]
         return [getattr(self, n) for n in names if hasattr(self, n)]
 
-    # One slab-reduce launch per backward segment instead of one behind every weight gradient (108 launches of
-    # ~6 us per SlowFast-R50 step).  Measured SLOWER (A/B on one box, 30 steps: 14.00 ms batched vs 13.77 ms): the
-    # per-layer reduce reads slabs its wgrad wrote microseconds earlier (L2 / Infinity Cache), the batched one
-    # reads 1.45 GB back from HBM and competes with the BN passes.  Kept behind VS_WGRAD_BATCH=1.
-    batch_wgrads = os.environ.get("VS_WGRAD_BATCH", "0") == "1"
-    _reduce_streams = {}
-
-    def _flush_wgrads(self, last):
-        """Sum the pending weight-gradient slabs.  The launch goes to a side stream beside the next segment; it
-        is joined at the end of the backward pass -- or at once when the segments are driven from outside
-        (`defer_backward`: the caller all-reduces the segment's gradients right behind it)."""
-        batch = self._wgrad_batch
-        if batch is None or (not batch.pending and not self._reduce_pending):
-            return
-        if ops._WHATIF & 4:  # timing experiment only: the slabs are never summed (garbage gradients)
-            batch.pending.clear() if hasattr(batch.pending, "clear") else None
-            return
-        main = torch.cuda.current_stream()
-        key = main.device.index
-        rs = VideoTrunk._reduce_streams.get(key)
-        if rs is None:
-            rs = VideoTrunk._reduce_streams[key] = torch.cuda.Stream(device=main.device)
-        if batch.pending:
-            rs.wait_stream(main)
-            with torch.cuda.stream(rs):
-                batch.flush()
-            self._reduce_pending = True
-        if self._reduce_pending and (last or self.defer_backward):
-            main.wait_stream(rs)
-            self._reduce_pending = False
-
     def _backward_segment(self, st, seg):
-        if self.batch_wgrads and st["d"][0].is_cuda:
-            if self._wgrad_batch is None:
-                self._wgrad_batch = ops.WgradBatch()
-            _Unit.wgrad_batch = self._wgrad_batch
         # Slab reduces of weight gradients issued on this thread's streams wait for the next unit's BN-backward finalize
         # and share its launch (ops.REDUCE_MERGE, vs_wgrad_reduce_defer): ~70 launches fewer on the step's chain.
         # Whatever is still pending at the end of the segment is launched there (the caller may all-reduce next).
-        merge = ops.REDUCE_MERGE and st["d"][0].is_cuda and not self.batch_wgrads
+        merge = ops.REDUCE_MERGE and st["d"][0].is_cuda
         if merge:
             ops.wgrad_reduce_defer(1)
             _WgradLanes.defer_active = True
         try:
             self._backward_segment_body(st, seg)
         finally:
-            _Unit.wgrad_batch = None
             if merge:
                 _WgradLanes.defer_active = False
                 ops.wgrad_reduce_defer(0)  # flushes
-        self._flush_wgrads(last=seg == self.BWD_SEGMENTS[-1])
 
     def _backward_segment_body(self, st, seg):
         for k in {"s5": (5,), "s4": (4,), "rest": (3, 2)}[seg]:

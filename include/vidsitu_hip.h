@@ -495,6 +495,26 @@ int vs_adam_tick(int* step_counter, void* stream);
 int vs_adam_step_dev_range(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16, int64_t n,
                            float lr, float beta1, float beta2, float eps, const int* step_counter,
                            float grad_scale, void* stream);
+/* Adam with its hyper-parameters in device memory (`float hyper[8]`, owned by the caller), so that a captured launch
+ * follows a learning-rate schedule (utils/trn_utils.py:896-912), and with torch's weight decay and global-norm clip:
+ *   hyper[0] lr (read)   hyper[1] weight_decay (read)   hyper[2] max_grad_norm, <= 0: no clipping (read)
+ *   hyper[3] global gradient norm of this step (written)   hyper[4] clip coefficient applied (written)   [5..7] zero
+ * vs_grad_sumsq writes the sum of squares of a gradient arena (fp32, or bf16 when g_is_bf16) as fp64 partial sums over a
+ * partition of [0, n) that depends on n alone; every product and sum is fp64, the order of additions is fixed and no
+ * atomics are used: the same bits from run to run.  workspace: vs_grad_sumsq_workspace_bytes(n) bytes, 8-byte aligned.
+ * vs_adam_step_hp is the update of vs_adam_step_dev* (g fp32 or bf16, p_bf16 may be NULL; tick != 0 increments the step
+ * count first, tick == 0 is the ranged form against an already ticked count) with lr = hyper[0].  With sumsq_ws (the
+ * workspace vs_grad_sumsq filled for the WHOLE arena, also in a ranged call) each block adds the partials up in one
+ * fixed order, norm = grad_scale * sqrt(sum), coef = min(1, max_norm / (norm + 1e-6)) as torch's clip_grad_norm_, and
+ * hyper[3], hyper[4] are written; the gradient used is (g * grad_scale) * coef, coef exactly 1 without a workspace,
+ * without a limit or under it.  hyper[1] != 0 adds weight decay: flags bit 0 clear, torch.optim.Adam's g += wd * p
+ * (after the clip); set, AdamW's p *= 1 - lr * wd (before the update).  With hyper[1] == 0 and coef == 1 the results
+ * are those of vs_adam_step_dev* bit for bit. */
+int64_t vs_grad_sumsq_workspace_bytes(int64_t n);
+int vs_grad_sumsq(const void* g, int g_is_bf16, int64_t n, void* workspace, int64_t ws_bytes, void* stream);
+int vs_adam_step_hp(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16, int64_t n, float* hyper,
+                    float beta1, float beta2, float eps, int* step_counter, int tick, float grad_scale, int flags,
+                    const void* sumsq_ws, void* stream);
 /* fp32 -> bf16 cast of the parameter arena (weights used by the conv kernels). */
 int vs_cast_f32_to_bf16(const float* x, void* y, int64_t n, void* stream);
 

@@ -7,6 +7,11 @@ Kept: uid + dotted overrides, `num_gpus` from the visible devices, one process p
 localhost TCP rendezvous and backend `cfg.DIST_BACKEND` ("nccl" == RCCL on ROCm;
 `utils/trn_dist_utils.py:5-42`), `get_mdl_loss_eval` plugin lookup, Adam(betas=(0.9, 0.99)) at
 `train.lr`, per-rank batch = `train.bs // num_gpus` (`utils/dat_utils.py:42-43`).
+`train.weight_decay` / `train.decoupled_weight_decay` / `train.max_grad_norm` configure the optimizer;
+`train.warmup_it` warms the rate up per iteration; `--val_every=N` (default 0: no validation inside the loop) runs the
+validation every N steps and, with `train.use_reduce_lr_plateau`, feeds its loss to ReduceLROnPlateau
+(`cfg.reduce_factor`, `cfg.patience`; `utils/trn_utils.py:896-912`).  The rate is a device float the captured step
+reads, so the same graphs go on replaying after a change; the schedule's state is saved with the checkpoint.
 `train.resume` / `train.resume_path` / `train.load_opt` / `train.strict_load` restore a checkpoint in the
 reference's file format before training and `misc.tmp_path/models/<uid>.pth` is written after it
 (`vidsitu_amd/checkpoint.py`; `utils/trn_utils.py:631-716`).
@@ -37,7 +42,7 @@ import time
 import torch
 import torch.distributed as dist
 
-from vidsitu_amd import checkpoint, dist_launch, synth_data
+from vidsitu_amd import checkpoint, dist_launch, lr_sched, synth_data
 from vidsitu_amd.extended_config import get_cfg
 from vidsitu_amd.mdl_selector import get_mdl_loss_eval
 from vidsitu_amd.optim import ArenaAdam, ParamArena
@@ -51,7 +56,34 @@ def _load_batch(static, new):
             v.copy_(new[k], non_blocking=True)
 
 
-def main_fn(rank, cfg, steps, graph=True):
+def build_optimizer(cfg, arena):
+    """ArenaAdam from `train.lr / weight_decay / decoupled_weight_decay / max_grad_norm`; the rate lives in device
+    memory (`dynamic_lr`) when a schedule will change it.  Every key is read with a default: the reference's own
+    config file has none of the additions."""
+    tr = cfg.train
+    scheduled = bool(tr.get("use_reduce_lr_plateau", False)) or int(tr.get("warmup_it", 0) or 0) > 0
+    mgn = float(tr.get("max_grad_norm", 0.0) or 0.0)
+    return ArenaAdam(arena, lr=tr.lr, betas=(0.9, 0.99), weight_decay=float(tr.get("weight_decay", 0.0) or 0.0),
+                     decoupled_weight_decay=bool(tr.get("decoupled_weight_decay", False)),
+                     max_grad_norm=mgn if mgn > 0 else None, dynamic_lr=scheduled)
+
+
+def build_schedulers(cfg, opt):
+    """(warm-up stepped every iteration | None, plateau schedule stepped on the validation loss | None) --
+    `prepare_scheduler` (`utils/trn_utils.py:896-912`): ReduceLROnPlateau(factor=cfg.reduce_factor,
+    patience=cfg.patience) when `train.use_reduce_lr_plateau`, else a LambdaLR."""
+    tr = cfg.train
+    warm = None
+    if int(tr.get("warmup_it", 0) or 0) > 0:
+        warm = lr_sched.LambdaLR(opt, lr_sched.warmup_linear(int(tr.warmup_it)))
+    plateau = None
+    if tr.get("use_reduce_lr_plateau", False):
+        plateau = lr_sched.ReduceLROnPlateau(opt, mode="min", factor=float(cfg.get("reduce_factor", 0.1)),
+                                             patience=int(cfg.get("patience", 10)))
+    return warm, plateau
+
+
+def main_fn(rank, cfg, steps, graph=True, val_every=0):
     world = cfg.num_gpus
     # the device index is the rank's place on ITS node (LOCAL_RANK, set by dist_launch.rank_env and by
     # torch.distributed.run); RANK only equals it on one node
@@ -70,17 +102,26 @@ def main_fn(rank, cfg, steps, graph=True):
     eval_fn = sel["evl"](cfg, comm, dev)
     arena = ParamArena(mdl)
     arena.broadcast_params(0)
-    opt = ArenaAdam(arena, lr=cfg.train.lr, betas=(0.9, 0.99))
+    opt = build_optimizer(cfg, arena)
+    warm, plateau = build_schedulers(cfg, opt)
+    warmup_it = int(cfg.train.get("warmup_it", 0) or 0)
     num_it = 0
     model_file = f"{cfg.misc.tmp_path}/models/{cfg.uid}.pth"
     if cfg.train.resume:
         rpath = cfg.train.resume_path or model_file  # "" -> this run's own model file
         got = checkpoint.load_model_dict(rpath, mdl, opt, load_opt=cfg.train.load_opt,
-                                         strict=cfg.train.strict_load, arena=arena)
+                                         strict=cfg.train.strict_load, arena=arena, scheduler=plateau)
         if got is not None:
             num_it = got["num_it"] or 0
+            if warm is not None and cfg.train.load_opt:
+                # the warm-up is a function of the iteration: pick it up where the file stopped (a finished one
+                # leaves the restored rate alone)
+                warm.last_epoch = min(num_it, warmup_it)
+                if num_it < warmup_it:
+                    warm.last_epoch = num_it - 1
+                    warm.step()
             if rank == 0:
-                print(f"[{cfg.uid}] resumed {rpath} at iteration {num_it}")
+                print(f"[{cfg.uid}] resumed {rpath} at iteration {num_it}, lr {opt.lr:g}")
         elif rank == 0:
             print(f"[{cfg.uid}] no existing model in {rpath}, starting from scratch")
     elif cfg.mdl.load_sf_pretrained and cfg.task_type == "vb":  # Kinetics init of the trunk (utils/trn_utils.py:358-375)
@@ -120,6 +161,23 @@ def main_fn(rank, cfg, steps, graph=True):
                     t0, timed_from = time.time(), it
                 ts.run()
                 losses.append(ts.loss.clone())
+                if warm is not None and warm.last_epoch < warmup_it:
+                    warm.step()  # one fill of a device float: the replayed graph reads it
+                    if plateau is not None:
+                        plateau._last_lr = [opt.lr]
+                if val_every > 0 and (it + 1) % val_every == 0 and it + 1 < steps:
+                    # `Learner.fit`'s validation between training steps; the same graphs go on replaying afterwards
+                    val_loss = eval_fn(mdl, loss_fn, batches, "valid", rank)[0]["loss"]
+                    mdl.train()
+                    if cfg.do_dist:  # every rank must take the same decision
+                        vl = torch.tensor([val_loss], dtype=torch.float64, device=dev)
+                        dist.all_reduce(vl)
+                        val_loss = float(vl) / world
+                    if plateau is not None:
+                        before = opt.lr
+                        plateau.step(val_loss)
+                        if rank == 0 and opt.lr != before:
+                            print(f"[{cfg.uid}] it {num_it + it + 1}: valid loss {val_loss:.4f}, lr {before:g} -> {opt.lr:g}")
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         t_run = time.time() - t0
@@ -130,7 +188,7 @@ def main_fn(rank, cfg, steps, graph=True):
                   f"{'bf16' if ts.grad_bf16 else 'fp32'} gradient payload, world {world}), "
                   f"{bs * n_ev * world * (steps - timed_from) / t_run:.1f} clips/s over the last {steps - timed_from} "
                   f"step(s), loss {ls[0]} -> {ls[-1]}")
-            checkpoint.save_model_dict(model_file, mdl, opt, num_it=num_it + steps, cfg=None)
+            checkpoint.save_model_dict(model_file, mdl, opt, num_it=num_it + steps, cfg=None, scheduler=plateau)
             print(f"[{cfg.uid}] saved {model_file}")
     loss_d, acc_d = eval_fn(mdl, loss_fn, batches, "valid", rank)
     if rank == 0:
@@ -143,6 +201,7 @@ def main_fn(rank, cfg, steps, graph=True):
 def main_dist(uid, **kwargs):
     steps = int(kwargs.pop("steps", 10))
     graph = kwargs.pop("graph", None)
+    val_every = int(kwargs.pop("val_every", 0))
     cfg = get_cfg(kwargs)
     # hipGraph replay is the default for the verb-prediction rows (the measured step); the SRL rows (`vb_arg`) keep an
     # eager TrainStep unless --graph=1 asks for a capture (which raises if the model syncs with the host)
@@ -169,12 +228,12 @@ def main_dist(uid, **kwargs):
         # the parent never touches the GPU: one fresh interpreter per rank
         sys.exit(dist_launch.launch_ranks(want, [sys.executable, os.path.abspath(__file__)] + sys.argv[1:],
                                           port=int(os.environ.get("MASTER_PORT", 0)) or None))
-    main_fn(int(os.environ.get("RANK", "0")) if in_rank else 0, cfg, steps, graph)
+    main_fn(int(os.environ.get("RANK", "0")) if in_rank else 0, cfg, steps, graph, val_every)
 
 
 if __name__ == "__main__":
     if len(sys.argv) < 2:
-        sys.exit("usage: main_dist.py <uid> [--dotted.key=value ...] [--steps=N] [--graph=0|1]")
+        sys.exit("usage: main_dist.py <uid> [--dotted.key=value ...] [--steps=N] [--graph=0|1] [--val_every=N]")
     kw = {}
     for a in sys.argv[2:]:
         assert a.startswith("--") and "=" in a, f"bad argument {a}"

@@ -34,8 +34,9 @@ def reference_only_keys(mdl):
     return out
 
 
-def save_model_dict(path, mdl, optimizer=None, num_it=0, num_epoch=0, best_met=None, cfg=None):
-    """`Learner.save_model_dict` (`trn_utils.py:699-716`)."""
+def save_model_dict(path, mdl, optimizer=None, num_it=0, num_epoch=0, best_met=None, cfg=None, scheduler=None):
+    """`Learner.save_model_dict` (`trn_utils.py:699-716`).  `scheduler`: a schedule of `vidsitu_amd.lr_sched` (or
+    torch's); its `state_dict()` is written as `scheduler_state_dict`, as the reference does."""
     msd = {k: v.detach().cpu().contiguous() for k, v in mdl.state_dict().items()}
     for k, shape in reference_only_keys(mdl).items():  # placeholders the reference's strict load expects
         msd.setdefault(k, torch.zeros(shape))
@@ -49,15 +50,18 @@ def save_model_dict(path, mdl, optimizer=None, num_it=0, num_epoch=0, best_met=N
                 if torch.is_tensor(v):
                     st[k] = v.detach().cpu()
         ckpt["optimizer_state_dict"] = sd
+    if scheduler is not None:
+        ckpt["scheduler_state_dict"] = scheduler.state_dict()
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "wb") as f:
         torch.save(ckpt, f)
     return ckpt
 
 
-def load_model_dict(path, mdl, optimizer=None, load_opt=False, strict=True, arena=None):
+def load_model_dict(path, mdl, optimizer=None, load_opt=False, strict=True, arena=None, scheduler=None):
     """`Learner.load_model_dict` (`trn_utils.py:631-697`): a missing file means "start from scratch"
-    (returns None); otherwise the model (and, with load_opt, the optimizer) is restored in place and
+    (returns None); otherwise the model (and, with load_opt, the optimizer and -- when the file holds its state -- the
+    `scheduler`) is restored in place and
     the bookkeeping {"num_it", "num_epoch", "best_met"} returned.  `arena`: the ParamArena the
     parameters live in -- its bf16 / transposed kernel copies are refreshed after the load."""
     if not os.path.exists(path):
@@ -94,6 +98,8 @@ def load_model_dict(path, mdl, optimizer=None, load_opt=False, strict=True, aren
         if optimizer is None or "optimizer_state_dict" not in ckpt:
             raise ValueError("load_opt needs an optimizer and a checkpoint that holds its state")
         optimizer.load_state_dict(ckpt["optimizer_state_dict"])
+        if scheduler is not None and "scheduler_state_dict" in ckpt:  # `trn_utils.py:704-706`
+            scheduler.load_state_dict(ckpt["scheduler_state_dict"])
     return {k: ckpt.get(k) for k in ("num_it", "num_epoch", "best_met")}
 
 

@@ -1678,6 +1678,254 @@ extern "C" int vs_adam_step_dev_range(float* p, const void* g, int g_is_bf16, fl
                          grad_scale, stream, false);
 }
 
+// ----------------------------------------------------------------------------
+// Adam with its hyper-parameters in device memory: learning rate, weight decay and the global-norm clip are read by
+// the kernel from `float hyper[8]`, so a captured launch follows whatever the host wrote there before the replay.
+//   hyper[0] lr   [1] weight_decay   [2] max_grad_norm (<= 0: no clip)   [3] <- gradient norm   [4] <- clip coefficient
+// The norm is a two-kernel reduction with the second half folded into the update (the launch-boundary reduce):
+// grad_sumsq_kernel writes VS_SUMSQ_PARTS fp64 partial sums, every block of adam_hp_kernel adds them up in one fixed
+// order in its prologue.  No atomics, no cross-block handshake: the same bits from run to run.
+// ----------------------------------------------------------------------------
+#define VS_SUMSQ_PARTS 1024
+#define VS_SUMSQ_ALIGN 2048  // a partial covers a multiple of this many elements: a chunk starts as aligned as the arena
+
+// [0, n) in at most VS_SUMSQ_PARTS chunks of equal length: a function of n alone.
+static long long sumsq_chunk(long long n) {
+  const long long per = (n + VS_SUMSQ_PARTS - 1) / VS_SUMSQ_PARTS;
+  return (per + VS_SUMSQ_ALIGN - 1) / VS_SUMSQ_ALIGN * VS_SUMSQ_ALIGN;
+}
+
+// The sum of one block's 256 fp64 values in a fixed order: lanes by halving strides, then the four waves in index order.
+__device__ __forceinline__ double block_sum_f64(double s, double* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// Block k sums the squares of chunk k (zero for a chunk past the end, so that the reader needs no count).  A thread adds
+// its head elements, then its vector groups (four 16-byte / 8-byte loads in flight, one accumulator each), then its tail
+// element, every product and every sum in fp64.  Plain loads: the update reads the same gradients right after.
+template <bool G16>
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const void* gv, long long n, long long chunk,
+                                                         double* partial) {
+  __shared__ double red[4];
+  const long long lo = (long long)blockIdx.x * chunk;
+  const int t = threadIdx.x;
+  double acc = 0.0;
+  if (lo < n) {
+    const long long len = (lo + chunk < n ? lo + chunk : n) - lo;
+    const float* g = (const float*)gv + lo;
+    const uint16_t* gh = (const uint16_t*)gv + lo;
+    auto at = [&](long long i) __attribute__((always_inline)) {
+      return (double)(G16 ? bf16_to_f32(gh[i]) : g[i]);
+    };
+    const uintptr_t addr = G16 ? (uintptr_t)gh : (uintptr_t)g;
+    long long head;  // elements in front of the first vector boundary; everything when the view cannot be vectorised
+    if (G16) head = (addr & 1) ? len : (long long)(((8 - (addr & 7)) & 7) >> 1);
+    else head = (addr & 3) ? len : (long long)(((16 - (addr & 15)) & 15) >> 2);
+    if (head > len) head = len;
+    const long long nvec = (len - head) / 4;
+    for (long long i = t; i < head; i += 256) {
+      const double x = at(i);
+      acc = fma(x, x, acc);
+    }
+    double a[4] = {0.0, 0.0, 0.0, 0.0};
+    auto group = [&](long long j, double s) __attribute__((always_inline)) {
+      float x[4];
+      if (G16) {
+        const uint2 w = ((const uint2*)(gh + head))[j];
+        x[0] = __uint_as_float(w.x << 16); x[1] = __uint_as_float(w.x & 0xffff0000u);
+        x[2] = __uint_as_float(w.y << 16); x[3] = __uint_as_float(w.y & 0xffff0000u);
+      } else {
+        const float4 w = ((const float4*)(g + head))[j];
+        x[0] = w.x; x[1] = w.y; x[2] = w.z; x[3] = w.w;
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s = fma((double)x[e], (double)x[e], s);
+      return s;
+    };
+    long long j = t;
+    for (; j + 768 < nvec; j += 1024) {
+      const double s0 = group(j, a[0]), s1 = group(j + 256, a[1]), s2 = group(j + 512, a[2]), s3 = group(j + 768, a[3]);
+      a[0] = s0; a[1] = s1; a[2] = s2; a[3] = s3;
+    }
+    for (; j < nvec; j += 256) a[0] = group(j, a[0]);
+    acc += (a[0] + a[1]) + (a[2] + a[3]);
+    const long long i = head + nvec * 4 + t;
+    if (i < len) {
+      const double x = at(i);
+      acc = fma(x, x, acc);
+    }
+  }
+  const double s = block_sum_f64(acc, red);
+  if (t == 0) partial[blockIdx.x] = s;
+}
+
+extern "C" int64_t vs_grad_sumsq_workspace_bytes(int64_t n) {
+  return n > 0 ? (int64_t)(VS_SUMSQ_PARTS * sizeof(double)) : 0;
+}
+
+extern "C" int vs_grad_sumsq(const void* g, int g_is_bf16, int64_t n, void* workspace, int64_t ws_bytes,
+                             void* stream) {
+  VS_CHECK_ARG(g && workspace && n > 0, "bad args");
+  VS_CHECK_ARG(ws_bytes >= vs_grad_sumsq_workspace_bytes(n) && (((uintptr_t)workspace) & 7) == 0,
+               "workspace smaller than vs_grad_sumsq_workspace_bytes(n), or not 8-byte aligned");
+  const long long chunk = sumsq_chunk((long long)n);
+  if (g_is_bf16)
+    hipLaunchKernelGGL(grad_sumsq_kernel<true>, dim3(VS_SUMSQ_PARTS), dim3(256), 0, (hipStream_t)stream, g,
+                       (long long)n, chunk, (double*)workspace);
+  else
+    hipLaunchKernelGGL(grad_sumsq_kernel<false>, dim3(VS_SUMSQ_PARTS), dim3(256), 0, (hipStream_t)stream, g,
+                       (long long)n, chunk, (double*)workspace);
+  VS_CHECK_LAUNCH();
+  return VS_OK;
+}
+
+// adam_dev_kernel's loops with the clip coefficient and one of three decay forms compiled in.  DECAY 0: none -- the
+// arithmetic per element is adam_dev_kernel's, and with coef == 1.0f so are the bits; 1: torch.optim.Adam's L2 form,
+// g += wd * p after the clip; 2: AdamW's, p *= 1 - lr * wd before the update.
+template <bool G16, int DECAY>
+__device__ __forceinline__ void adam_hp_body(float* p, const void* gv, float* m, float* v, uint16_t* pb, long long n4,
+                                             long long n, float lr, float wd, float a, float b1, float b2, float eps,
+                                             float bc2_sqrt, float grad_scale, float coef) {
+  const float* g = (const float*)gv;
+  const uint16_t* gh = (const uint16_t*)gv;
+  const float shrink = 1.f - lr * wd;
+  typedef __attribute__((ext_vector_type(4))) float nt_f4;
+  typedef __attribute__((ext_vector_type(2))) unsigned nt_u2;
+  auto ldnt = [](const float* q, long long i) __attribute__((always_inline)) {
+    const nt_f4 t = __builtin_nontemporal_load((const nt_f4*)q + i);
+    return make_float4(t[0], t[1], t[2], t[3]);
+  };
+  auto stnt = [](float* q, long long i, float a0, float a1, float a2, float a3) __attribute__((always_inline)) {
+    const nt_f4 t = {a0, a1, a2, a3};
+    __builtin_nontemporal_store(t, (nt_f4*)q + i);
+  };
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x; i0 < n4; i0 += 2 * stride) {
+    const long long i1 = i0 + stride;
+    const bool two = i1 < n4;
+    const long long j1 = two ? i1 : i0;
+    float gg[2][4];
+    if (G16) {
+      const nt_u2 ga_ = __builtin_nontemporal_load((const nt_u2*)gv + i0), gb_ = __builtin_nontemporal_load((const nt_u2*)gv + j1);
+      const uint2 ga = make_uint2(ga_[0], ga_[1]), gb = make_uint2(gb_[0], gb_[1]);
+      gg[0][0] = __uint_as_float(ga.x << 16) * grad_scale;
+      gg[0][1] = __uint_as_float(ga.x & 0xffff0000u) * grad_scale;
+      gg[0][2] = __uint_as_float(ga.y << 16) * grad_scale;
+      gg[0][3] = __uint_as_float(ga.y & 0xffff0000u) * grad_scale;
+      gg[1][0] = __uint_as_float(gb.x << 16) * grad_scale;
+      gg[1][1] = __uint_as_float(gb.x & 0xffff0000u) * grad_scale;
+      gg[1][2] = __uint_as_float(gb.y << 16) * grad_scale;
+      gg[1][3] = __uint_as_float(gb.y & 0xffff0000u) * grad_scale;
+    } else {
+      const float4 ga = ldnt((const float*)gv, i0), gb = ldnt((const float*)gv, j1);
+      gg[0][0] = ga.x * grad_scale; gg[0][1] = ga.y * grad_scale; gg[0][2] = ga.z * grad_scale; gg[0][3] = ga.w * grad_scale;
+      gg[1][0] = gb.x * grad_scale; gg[1][1] = gb.y * grad_scale; gg[1][2] = gb.z * grad_scale; gg[1][3] = gb.w * grad_scale;
+    }
+    const float4 ma = ldnt(m, i0), va = ldnt(v, i0), pa = ((float4*)p)[i0];
+    const float4 mb = ldnt(m, j1), vb = ldnt(v, j1), pq = ((float4*)p)[j1];
+    float mm[2][4] = {{ma.x, ma.y, ma.z, ma.w}, {mb.x, mb.y, mb.z, mb.w}};
+    float vv[2][4] = {{va.x, va.y, va.z, va.w}, {vb.x, vb.y, vb.z, vb.w}};
+    float pp[2][4] = {{pa.x, pa.y, pa.z, pa.w}, {pq.x, pq.y, pq.z, pq.w}};
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        gg[u][e] = gg[u][e] * coef;
+        if (DECAY == 1) gg[u][e] += wd * pp[u][e];
+        if (DECAY == 2) pp[u][e] *= shrink;
+        mm[u][e] = b1 * mm[u][e] + (1.f - b1) * gg[u][e];
+        vv[u][e] = b2 * vv[u][e] + (1.f - b2) * gg[u][e] * gg[u][e];
+        const float denom = sqrtf(vv[u][e]) / bc2_sqrt + eps;
+        pp[u][e] -= a * (mm[u][e] / denom);
+      }
+    stnt(m, i0, mm[0][0], mm[0][1], mm[0][2], mm[0][3]);
+    stnt(v, i0, vv[0][0], vv[0][1], vv[0][2], vv[0][3]);
+    ((float4*)p)[i0] = make_float4(pp[0][0], pp[0][1], pp[0][2], pp[0][3]);
+    if (pb) ((uint2*)pb)[i0] = make_uint2(pack2_bf16(pp[0][0], pp[0][1]), pack2_bf16(pp[0][2], pp[0][3]));
+    if (two) {
+      stnt(m, i1, mm[1][0], mm[1][1], mm[1][2], mm[1][3]);
+      stnt(v, i1, vv[1][0], vv[1][1], vv[1][2], vv[1][3]);
+      ((float4*)p)[i1] = make_float4(pp[1][0], pp[1][1], pp[1][2], pp[1][3]);
+      if (pb) ((uint2*)pb)[i1] = make_uint2(pack2_bf16(pp[1][0], pp[1][1]), pack2_bf16(pp[1][2], pp[1][3]));
+    }
+  }
+  // scalar tail (n not a multiple of 4, or unaligned buffers: then n4 == 0 and this is everything)
+  for (long long i = n4 * 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (long long)gridDim.x * blockDim.x) {
+    float gi = ((G16 ? bf16_to_f32(gh[i]) : g[i]) * grad_scale) * coef;
+    float pi = p[i];
+    if (DECAY == 1) gi += wd * pi;
+    if (DECAY == 2) pi *= shrink;
+    const float mi = b1 * m[i] + (1.f - b1) * gi;
+    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    pi = pi - a * (mi / denom);
+    p[i] = pi;
+    if (pb) pb[i] = f32_to_bf16(pi);
+  }
+}
+
+template <bool G16>
+__global__ __launch_bounds__(256) void adam_hp_kernel(float* p, const void* gv, float* m, float* v, uint16_t* pb,
+                                                      long long n4, long long n, float* hyper, float b1, float b2,
+                                                      float eps, const int* step, float grad_scale, int flags,
+                                                      const double* ws) {
+  __shared__ double red[4];
+  const float lr = hyper[0], wd = hyper[1], max_norm = hyper[2];
+  float coef = 1.f;
+  if (ws) {  // kernel-uniform: every block forms the same norm from the same partials in the same order
+    const double* q = ws + 4 * threadIdx.x;
+    const double sum = block_sum_f64(((q[0] + q[1]) + q[2]) + q[3], red);
+    const float norm = (float)((double)grad_scale * sqrt(sum));
+    if (max_norm > 0.f) coef = fminf(1.f, max_norm / (norm + 1e-6f));
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      hyper[3] = norm;
+      hyper[4] = coef;
+    }
+  }
+  const float t = (float)step[0];
+  const float bc1 = 1.f - powf(b1, t);
+  const float bc2_sqrt = sqrtf(1.f - powf(b2, t));
+  const float a = lr / bc1;
+  if (wd == 0.f)
+    adam_hp_body<G16, 0>(p, gv, m, v, pb, n4, n, lr, wd, a, b1, b2, eps, bc2_sqrt, grad_scale, coef);
+  else if (flags & 1)
+    adam_hp_body<G16, 2>(p, gv, m, v, pb, n4, n, lr, wd, a, b1, b2, eps, bc2_sqrt, grad_scale, coef);
+  else
+    adam_hp_body<G16, 1>(p, gv, m, v, pb, n4, n, lr, wd, a, b1, b2, eps, bc2_sqrt, grad_scale, coef);
+}
+
+extern "C" int vs_adam_step_hp(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16, int64_t n,
+                               float* hyper, float beta1, float beta2, float eps, int* step_counter, int tick,
+                               float grad_scale, int flags, const void* sumsq_ws, void* stream) {
+  VS_CHECK_ARG(p && g && m && v && n > 0 && hyper && step_counter, "bad args");
+  VS_CHECK_ARG((flags & ~1) == 0 && (((uintptr_t)sumsq_ws) & 7) == 0, "unknown flag bits, or a misaligned sum-of-squares workspace");
+  const bool g16 = g_is_bf16 != 0;
+  const bool aligned = (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) == 0 &&
+                       (((uintptr_t)g) & (g16 ? 7 : 15)) == 0 && (((uintptr_t)p_bf16) & 7) == 0;
+  const long long n4 = aligned ? n / 4 : 0;
+  long long grid = ((aligned ? n4 : (long long)n) + 255) / 256;
+  if (grid > 4096) grid = 4096;
+  if (grid < 1) grid = 1;
+  if (tick) hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_counter);
+  if (g16)
+    hipLaunchKernelGGL(adam_hp_kernel<true>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                       (uint16_t*)p_bf16, n4, (long long)n, hyper, beta1, beta2, eps, (const int*)step_counter,
+                       grad_scale, flags, (const double*)sumsq_ws);
+  else
+    hipLaunchKernelGGL(adam_hp_kernel<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                       (uint16_t*)p_bf16, n4, (long long)n, hyper, beta1, beta2, eps, (const int*)step_counter,
+                       grad_scale, flags, (const double*)sumsq_ws);
+  VS_CHECK_LAUNCH();
+  return VS_OK;
+}
+
 __global__ void cast_f32_bf16_kernel(const float* x, uint16_t* y, long long n) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (long long)gridDim.x * blockDim.x)

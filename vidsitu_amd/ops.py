@@ -1130,6 +1130,35 @@ def adam_step_dev_range(p, g, m, v, p_bf16, lr, beta1, beta2, eps, step_counter,
               float(grad_scale), _stream())
 
 
+HYPER_LR, HYPER_WD, HYPER_MAX_NORM, HYPER_NORM, HYPER_COEF, HYPER_SLOTS = 0, 1, 2, 3, 4, 8
+ADAM_DECOUPLED = 1  # vs_adam_step_hp flags bit 0: AdamW's decay instead of torch.optim.Adam's L2 term
+
+
+def grad_sumsq_workspace(n, device):
+    """The fp64 partial sums `grad_sumsq` writes for an arena of n elements (allocated once: its address is captured)."""
+    nbytes = int(_lib.load().vs_grad_sumsq_workspace_bytes(int(n)))
+    return torch.zeros(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def grad_sumsq(g, workspace):
+    """Sum of squares of the gradient arena g (fp32 or bf16) as fp64 partials in `workspace` (bitwise reproducible);
+    `adam_step_hp` adds them up."""
+    _lib.call("vs_grad_sumsq", _ptr(g), int(g.dtype == BF16), g.numel(), _ptr(workspace),
+              workspace.numel() * workspace.element_size(), _stream())
+
+
+def adam_step_hp(p, g, m, v, p_bf16, hyper, beta1, beta2, eps, step_counter, tick=True, grad_scale=1.0,
+                 decoupled=False, sumsq_ws=None):
+    """Adam reading lr / weight decay / max_grad_norm from the device tensor `hyper` (float32[8]); with `sumsq_ws` (the
+    whole arena's partials from `grad_sumsq`) the global norm and clip coefficient are formed in the kernel and
+    written to hyper[3], hyper[4].  tick=False: one range against an already ticked step count."""
+    if hyper.dtype != torch.float32 or hyper.numel() < HYPER_SLOTS:
+        raise _lib.VsError("adam_step_hp: hyper must be a float32 tensor of 8 elements")
+    _lib.call("vs_adam_step_hp", _ptr(p), _ptr(g), int(g.dtype == BF16), _ptr(m), _ptr(v), _ptr(p_bf16), p.numel(),
+              _ptr(hyper), float(beta1), float(beta2), float(eps), _ptr(step_counter), int(bool(tick)),
+              float(grad_scale), ADAM_DECOUPLED if decoupled else 0, _ptr(sumsq_ws), _stream())
+
+
 def cast_bf16(src_f32, dst_bf16):
     _lib.call("vs_cast_f32_to_bf16", _ptr(src_f32), _ptr(dst_bf16), src_f32.numel(), _stream())
 

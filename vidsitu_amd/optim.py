@@ -319,13 +319,95 @@ class ParamArena:
             Conv3dP._pending_arenas.discard(self)
 
 class ArenaAdam:
-    """torch.optim.Adam semantics (lr, betas, eps; no weight decay) on the arena."""
+    """torch.optim.Adam / AdamW semantics on the arena.
 
-    def __init__(self, arena, lr=1e-4, betas=(0.9, 0.99), eps=1e-8):
-        self.arena, self.lr, self.betas, self.eps = arena, lr, betas, eps
+    With the defaults (no weight decay, no clipping, `dynamic_lr=False`) a step is the fused launch with the learning
+    rate as a launch argument -- fixed once the step is captured in a hipGraph.  Any other setting keeps the step's
+    hyper-parameters in device memory (`self.hyper`, float32[8]: lr, weight_decay, max_grad_norm, then the norm and
+    the clip coefficient the kernel writes back) and the update kernel reads them there (`vs_adam_step_hp`):
+      * `dynamic_lr=True`: `set_lr(x)` takes effect on the next step, replayed graphs included;
+      * `weight_decay`: torch.optim.Adam's L2 term, or AdamW's decay with `decoupled_weight_decay=True`;
+      * `max_grad_norm`: `torch.nn.utils.clip_grad_norm_` over the whole arena, computed and applied on the device
+        (`vs_grad_sumsq` before the update), so it is part of a captured step."""
+
+    def __init__(self, arena, lr=1e-4, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.0, decoupled_weight_decay=False,
+                 max_grad_norm=None, dynamic_lr=False):
+        self.arena, self._lr, self.betas, self.eps = arena, lr, betas, eps
         self.m = torch.zeros_like(arena.data)
         self.v = torch.zeros_like(arena.data)
         self.t = torch.zeros(1, dtype=torch.int32, device=arena.data.device)  # device-side: graph safe
+        self.weight_decay = float(weight_decay)
+        self.decoupled_weight_decay = bool(decoupled_weight_decay)
+        self.max_grad_norm = float(max_grad_norm) if max_grad_norm is not None and max_grad_norm > 0 else None
+        self.dynamic_lr = bool(dynamic_lr)
+        self.captured = False  # TrainStep.capture() sets it: a non-dynamic rate is frozen into the graph from then on
+        self.hyper, self.sumsq_ws = None, None
+        self._norm_due = True  # ranged steps: the norm pass runs before the first range after a tick()
+        if self.weight_decay < 0:
+            raise ValueError(f"weight_decay {weight_decay} < 0")
+        self._select_path()
+
+    # ---- the device-side hyper-parameter block ---------------------------------------------------
+    @property
+    def uses_hyper(self):
+        return self.hyper is not None
+
+    def _select_path(self):
+        """Allocate the hyper block (and the norm workspace) when a setting needs it: at construction, so that a
+        capture records fixed addresses."""
+        dev = self.arena.data.device
+        need = self.weight_decay != 0 or self.max_grad_norm is not None or self.dynamic_lr
+        if need and self.hyper is None:
+            self.hyper = torch.zeros(ops.HYPER_SLOTS, dtype=torch.float32, device=dev)
+        if self.hyper is not None:
+            self._write_hyper()
+        if self.max_grad_norm is not None and self.sumsq_ws is None and dev.type == "cuda":
+            self.sumsq_ws = ops.grad_sumsq_workspace(self.arena.numel, dev)
+
+    def _write_hyper(self):
+        vals = torch.zeros(ops.HYPER_SLOTS, dtype=torch.float32)
+        vals[ops.HYPER_LR], vals[ops.HYPER_WD] = float(self._lr), self.weight_decay
+        vals[ops.HYPER_MAX_NORM] = self.max_grad_norm if self.max_grad_norm is not None else 0.0
+        vals[ops.HYPER_COEF] = 1.0
+        self.hyper.copy_(vals)
+
+    @property
+    def lr(self):
+        return self._lr
+
+    @lr.setter
+    def lr(self, x):
+        """Plain assignment: on the launch-argument path the next eager step uses it (a captured one cannot:
+        `TrainStep.replay` refuses); on the device path it is `set_lr`."""
+        if self.hyper is not None:
+            self.set_lr(x)
+        else:
+            self._lr = x
+
+    def set_lr(self, x):
+        """The rate of every later step, stream-ordered: one fill of hyper[0] on the current stream."""
+        if self.arena.data.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ArenaAdam.set_lr during a graph capture: the fill would replay with every step")
+        if self.hyper is None:
+            if self.captured:
+                raise RuntimeError("ArenaAdam.set_lr: this optimizer's rate is a launch argument frozen into the "
+                                   "captured step; construct it with dynamic_lr=True")
+            self._lr = x
+            return
+        if self.captured and not self.dynamic_lr:
+            raise RuntimeError("ArenaAdam.set_lr on a captured optimizer without dynamic_lr=True")
+        self.hyper[ops.HYPER_LR:ops.HYPER_LR + 1].fill_(float(x))
+        self._lr = x
+
+    def last_grad_norm(self):
+        """Global gradient norm the last clipped step measured (synchronises: for logging)."""
+        if self.sumsq_ws is None:
+            raise RuntimeError("last_grad_norm: no max_grad_norm set, the norm is not computed")
+        return float(self.hyper[ops.HYPER_NORM].item())
+
+    def last_clip_coef(self):
+        """Clip coefficient the last step applied (1.0 without clipping; synchronises)."""
+        return float(self.hyper[ops.HYPER_COEF].item()) if self.hyper is not None else 1.0
 
     def zero_grad(self, fill=True):
         self.arena.zero_grad(fill)
@@ -353,7 +435,9 @@ class ArenaAdam:
             state[i] = {"step": torch.tensor(step),
                         "exp_avg": _dense_view(self.m, off, p).detach().clone().contiguous(),
                         "exp_avg_sq": _dense_view(self.v, off, p).detach().clone().contiguous()}
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0,
+        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps,
+                 "weight_decay": self.weight_decay if self.weight_decay != 0 else 0,
+                 "decoupled_weight_decay": self.decoupled_weight_decay,
                  "amsgrad": False, "params": list(range(len(index)))}
         return {"state": state, "param_groups": [group]}
 
@@ -371,9 +455,19 @@ class ArenaAdam:
             raise ValueError(f"optimizer state has {len(order)} parameters; the model has {len(index)} in the "
                              f"reference's order ({len(real)} of them built here)")
         g0 = groups[0]
-        self.lr, self.betas, self.eps = g0["lr"], tuple(g0["betas"]), g0["eps"]
-        if any(g.get("weight_decay", 0) != 0 or g.get("amsgrad", False) for g in groups):
-            raise ValueError("weight_decay / amsgrad are not implemented by the fused Adam kernel")
+        if any(g.get("amsgrad", False) for g in groups):
+            raise ValueError("amsgrad is not implemented by the fused Adam kernel")
+        hyper_keys = ("lr", "betas", "eps", "weight_decay", "decoupled_weight_decay")
+        norm = lambda g: tuple(tuple(g[k]) if k == "betas" else g.get(k, 0) or 0 for k in hyper_keys)  # noqa: E731
+        if any(norm(g) != norm(g0) for g in groups[1:]):
+            raise ValueError("parameter groups with different hyper-parameters: one set for the whole arena here")
+        wd, dec = float(g0.get("weight_decay", 0) or 0), bool(g0.get("decoupled_weight_decay", False))
+        if self.captured and (wd != self.weight_decay or (wd != 0 and dec != self.decoupled_weight_decay)):
+            raise ValueError("weight decay of the loaded state differs from the captured step's")
+        self.betas, self.eps = tuple(g0["betas"]), g0["eps"]
+        self.weight_decay, self.decoupled_weight_decay = wd, dec
+        self._lr = g0["lr"]
+        self._select_path()  # a state with weight decay moves a default optimizer onto the device-side path
         off_of = {id(p): off for p, off in zip(a.params, a.offsets)}
         self.m.zero_()
         self.v.zero_()
@@ -399,15 +493,32 @@ class ArenaAdam:
     def tick(self):
         """Start of a ranged step: the step count (device memory) goes up once."""
         ops.adam_tick(self.t)
+        self._norm_due = True
+
+    def _norm_pass(self, grad_bf16):
+        """The clip's sum of squares over the gradient arena the update reads (the arena's alignment gaps are zero:
+        `ParamArena.zero_grad`), as fp64 partials for the update kernel's prologue."""
+        if self.sumsq_ws is not None:
+            a = self.arena
+            ops.grad_sumsq(a.grad16 if grad_bf16 else a.grad, self.sumsq_ws)
 
     def step_range(self, lo, hi, world=1, grad_bf16=False):
         """The update of arena elements [lo, hi) against the count `tick()` set; no refresh of derived weight
-        images (the caller runs `finish_ranged()` once every range is done)."""
+        images (the caller runs `finish_ranged()` once every range is done).  With `max_grad_norm` the first range
+        after `tick()` runs the norm pass over the WHOLE arena: every gradient has to be final by then."""
         a = self.arena
         if hi <= lo:
             return
         g = (a.grad16 if grad_bf16 else a.grad)[lo:hi]
         pb = a.data_bf16[lo:hi] if a.data_bf16 is not None else None
+        if self.hyper is not None:
+            if self._norm_due:
+                self._norm_pass(grad_bf16)
+                self._norm_due = False
+            ops.adam_step_hp(a.data[lo:hi], g, self.m[lo:hi], self.v[lo:hi], pb, self.hyper, self.betas[0],
+                             self.betas[1], self.eps, self.t, tick=False, grad_scale=1.0 / world,
+                             decoupled=self.decoupled_weight_decay, sumsq_ws=self.sumsq_ws)
+            return
         ops.adam_step_dev_range(a.data[lo:hi], g, self.m[lo:hi], self.v[lo:hi], pb, self.lr, self.betas[0],
                                 self.betas[1], self.eps, self.t, grad_scale=1.0 / world)
 
@@ -423,6 +534,19 @@ class ArenaAdam:
         `arena.transposes_async()` at the start of the next step (bench.py).
         grad_bf16: the (all-reduced) gradients are read from the bf16 arena `arena.grad16`."""
         a = self.arena
+        if self.hyper is not None:
+            if a.data_bf16 is None and grad_bf16:
+                a.unpack_grad_bf16(0, a.numel)
+                grad_bf16 = False
+            self._norm_pass(grad_bf16)
+            ops.adam_step_hp(a.data, a.grad16 if grad_bf16 else a.grad, self.m, self.v, a.data_bf16, self.hyper,
+                             self.betas[0], self.betas[1], self.eps, self.t, tick=True, grad_scale=1.0 / world,
+                             decoupled=self.decoupled_weight_decay, sumsq_ws=self.sumsq_ws)
+            if a.data_bf16 is not None:
+                a.refresh(cast=False, transposes=not defer_transposes)
+            else:
+                a.refresh()
+            return
         if a.data_bf16 is not None:
             if grad_bf16:
                 ops.adam_step_dev_cast_g16(a.data, a.grad16, self.m, self.v, a.data_bf16, self.lr,

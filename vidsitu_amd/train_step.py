@@ -43,8 +43,15 @@ class TrainStep:
         self.overlap = (self.use_dist and world > 1 if overlap is None else bool(overlap)) and can_overlap
         # single process: ranged Adam beside the backward pass (needs the segmented backward and the arena on a GPU)
         want = os.environ.get("VS_ADAM_OVERLAP", "0") not in ("0", "") if adam_overlap is None else bool(adam_overlap)
+        if adam_overlap and getattr(opt, "max_grad_norm", None) is not None:
+            # the early ranges would be updated before the last segment's gradients -- part of the norm -- exist
+            raise ValueError("TrainStep: adam_overlap=True cannot be combined with the optimizer's max_grad_norm "
+                             "(the global norm is not known until the last segment)")
+        if getattr(opt, "max_grad_norm", None) is not None:
+            want = False  # (VS_ADAM_OVERLAP is an A/B switch of the default optimizer: a clipping step ignores it)
         self.adam_overlap = (want and not self.use_dist and can_overlap and arena.data.is_cuda
                              and hasattr(opt, "step_range"))
+        self._captured_lr = None
         self._adam_stream = None
         self.loss = None
         # The per-step memset of the gradient arena (300 MB for SlowFast-R50 + TxEncoder) is only needed by
@@ -252,6 +259,10 @@ class TrainStep:
                     graphs.append(g)
                 self.graphs = graphs
             torch.cuda.synchronize()
+            # a rate passed as a launch argument is frozen into the graph: replay() compares (see there)
+            self._captured_lr = getattr(self.opt, "lr", None)
+            if hasattr(self.opt, "captured"):
+                self.opt.captured = True
         except Exception as e:
             e = inner[0] if inner else e
             self.graphs = None
@@ -281,6 +292,10 @@ class TrainStep:
     def replay(self):
         if self.graphs is None:
             raise RuntimeError("replay() before capture()")
+        if not getattr(self.opt, "dynamic_lr", False) and getattr(self.opt, "lr", None) != self._captured_lr:
+            raise RuntimeError(f"TrainStep.replay: the optimizer's lr is {self.opt.lr!r} but the step was captured at "
+                               f"{self._captured_lr!r}, and this optimizer's rate is fixed at capture.  Build it with "
+                               "ArenaAdam(..., dynamic_lr=True) and change the rate with set_lr(), or capture again.")
         if not self.use_dist:
             self.graphs[0].replay()
             return

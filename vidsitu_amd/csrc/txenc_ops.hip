@@ -1528,19 +1528,39 @@ extern "C" int vs_adam_step(float* p, const float* g, float* m, float* v, int64_
 // otherwise replay the bias correction of the step it was captured at).
 __global__ void adam_tick_kernel(int* step) { step[0] += 1; }
 
-// float4-wide; optionally also emits the bf16 kernel copy of the updated parameters (saves the
-// separate cast pass over the arena).  G16: the gradients are bf16 (the summed payload of a bf16
-// all-reduce); parameters and both moments stay fp32.
-template <bool G16>
-__global__ void adam_dev_kernel(float* p, const void* gv, float* m, float* v, uint16_t* pb,
-                                long long n4, long long n, float lr, float b1, float b2, float eps,
-                                const int* step, float grad_scale) {
-  const float t = (float)step[0];
-  const float bc1 = 1.f - powf(b1, t);
-  const float bc2_sqrt = sqrtf(1.f - powf(b2, t));
-  const float a = lr / bc1;
+// Four bf16 values in two 32-bit words -> fp32 (a bf16 is the upper half of its fp32).
+__device__ __forceinline__ void bf16x4_to_f32(uint2 w, float x[4]) {
+  x[0] = __uint_as_float(w.x << 16); x[1] = __uint_as_float(w.x & 0xffff0000u);
+  x[2] = __uint_as_float(w.y << 16); x[3] = __uint_as_float(w.y & 0xffff0000u);
+}
+
+// The update of one element: the only copy of the arithmetic, called by the float4 loop and by the scalar tail of
+// adam_body.  g is the stored gradient, coef the clip coefficient (1.0f changes no bit).  DECAY 0: none; 1:
+// torch.optim.Adam's L2 form, g += wd * p after the clip; 2: AdamW's, p *= shrink (= 1 - lr * wd) before the update.
+// This file is compiled without multiply-add contraction: the spelling of these expressions fixes the bits.
+template <int DECAY>
+__device__ __forceinline__ void adam_update(float g, float& p, float& m, float& v, float grad_scale, float coef,
+                                            float wd, float shrink, float a, float b1, float b2, float eps,
+                                            float bc2_sqrt) {
+  g = (g * grad_scale) * coef;
+  if (DECAY == 1) g += wd * p;
+  if (DECAY == 2) p *= shrink;
+  m = b1 * m + (1.f - b1) * g;
+  v = b2 * v + (1.f - b2) * g * g;
+  const float denom = sqrtf(v) / bc2_sqrt + eps;
+  p -= a * (m / denom);
+}
+
+// The loops of both update kernels.  float4-wide; optionally also emits the bf16 kernel copy of the updated parameters
+// (saves the separate cast pass over the arena).  G16: the gradients are bf16 (the summed payload of a bf16
+// all-reduce); parameters and both moments stay fp32.  a = lr / bc1.
+template <bool G16, int DECAY>
+__device__ __forceinline__ void adam_body(float* p, const void* gv, float* m, float* v, uint16_t* pb, long long n4,
+                                          long long n, float lr, float wd, float a, float b1, float b2, float eps,
+                                          float bc2_sqrt, float grad_scale, float coef) {
   const float* g = (const float*)gv;
   const uint16_t* gh = (const uint16_t*)gv;
+  const float shrink = 1.f - lr * wd;
   // Two float4 groups per thread and iteration, all eight loads issued before the first use: with one group (four
   // loads, then ~40 dependent VALU instructions incl. a divide and a square root per element, then the stores) the
   // kernel moved its 1.1 GB at 2.4 TB/s.  Same arithmetic per element, same results bit for bit.
@@ -1549,133 +1569,71 @@ __global__ void adam_dev_kernel(float* p, const void* gv, float* m, float* v, ui
   // which the next step's first kernels read -- out of the Infinity Cache (profiles/r04_nontemporal.txt).
   typedef __attribute__((ext_vector_type(4))) float nt_f4;
   typedef __attribute__((ext_vector_type(2))) unsigned nt_u2;
-  auto ldnt = [](const float* q, long long i) __attribute__((always_inline)) {
+  auto ldnt = [](const float* q, long long i, float x[4]) __attribute__((always_inline)) {
     const nt_f4 t = __builtin_nontemporal_load((const nt_f4*)q + i);
-    return make_float4(t[0], t[1], t[2], t[3]);
+    x[0] = t[0]; x[1] = t[1]; x[2] = t[2]; x[3] = t[3];
   };
-  auto stnt = [](float* q, long long i, float a0, float a1, float a2, float a3) __attribute__((always_inline)) {
-    const nt_f4 t = {a0, a1, a2, a3};
-    __builtin_nontemporal_store(t, (nt_f4*)q + i);
+  auto ldg = [&](long long i, float x[4]) __attribute__((always_inline)) {
+    if (G16) {
+      const nt_u2 t = __builtin_nontemporal_load((const nt_u2*)gv + i);
+      bf16x4_to_f32(make_uint2(t[0], t[1]), x);
+    } else {
+      ldnt(g, i, x);
+    }
+  };
+  // group i: moments non-temporal, the parameters and their bf16 copy plain (they are read next)
+  auto put = [&](long long i, const float mm[4], const float vv[4], const float pp[4]) __attribute__((always_inline)) {
+    const nt_f4 tm = {mm[0], mm[1], mm[2], mm[3]}, tv = {vv[0], vv[1], vv[2], vv[3]};
+    __builtin_nontemporal_store(tm, (nt_f4*)m + i);
+    __builtin_nontemporal_store(tv, (nt_f4*)v + i);
+    ((float4*)p)[i] = make_float4(pp[0], pp[1], pp[2], pp[3]);
+    if (pb) ((uint2*)pb)[i] = make_uint2(pack2_bf16(pp[0], pp[1]), pack2_bf16(pp[2], pp[3]));
   };
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x; i0 < n4; i0 += 2 * stride) {
     const long long i1 = i0 + stride;
     const bool two = i1 < n4;
-    const long long j1 = two ? i1 : i0;
-    float gg[2][4];
-    if (G16) {
-      const nt_u2 ga_ = __builtin_nontemporal_load((const nt_u2*)gv + i0), gb_ = __builtin_nontemporal_load((const nt_u2*)gv + j1);
-      const uint2 ga = make_uint2(ga_[0], ga_[1]), gb = make_uint2(gb_[0], gb_[1]);
-      gg[0][0] = __uint_as_float(ga.x << 16) * grad_scale;
-      gg[0][1] = __uint_as_float(ga.x & 0xffff0000u) * grad_scale;
-      gg[0][2] = __uint_as_float(ga.y << 16) * grad_scale;
-      gg[0][3] = __uint_as_float(ga.y & 0xffff0000u) * grad_scale;
-      gg[1][0] = __uint_as_float(gb.x << 16) * grad_scale;
-      gg[1][1] = __uint_as_float(gb.x & 0xffff0000u) * grad_scale;
-      gg[1][2] = __uint_as_float(gb.y << 16) * grad_scale;
-      gg[1][3] = __uint_as_float(gb.y & 0xffff0000u) * grad_scale;
-    } else {
-      const float4 ga = ldnt((const float*)gv, i0), gb = ldnt((const float*)gv, j1);
-      gg[0][0] = ga.x * grad_scale; gg[0][1] = ga.y * grad_scale; gg[0][2] = ga.z * grad_scale; gg[0][3] = ga.w * grad_scale;
-      gg[1][0] = gb.x * grad_scale; gg[1][1] = gb.y * grad_scale; gg[1][2] = gb.z * grad_scale; gg[1][3] = gb.w * grad_scale;
-    }
-    const float4 ma = ldnt(m, i0), va = ldnt(v, i0), pa = ((float4*)p)[i0];
-    const float4 mb = ldnt(m, j1), vb = ldnt(v, j1), pq = ((float4*)p)[j1];
-    float mm[2][4] = {{ma.x, ma.y, ma.z, ma.w}, {mb.x, mb.y, mb.z, mb.w}};
-    float vv[2][4] = {{va.x, va.y, va.z, va.w}, {vb.x, vb.y, vb.z, vb.w}};
-    float pp[2][4] = {{pa.x, pa.y, pa.z, pa.w}, {pq.x, pq.y, pq.z, pq.w}};
+    const long long j1 = two ? i1 : i0;  // a lone last group is loaded and updated twice, stored once
+    float gg[2][4], mm[2][4], vv[2][4], pp[2][4];
+    ldg(i0, gg[0]);
+    ldg(j1, gg[1]);
+    ldnt(m, i0, mm[0]); ldnt(v, i0, vv[0]);
+    const float4 pa = ((float4*)p)[i0];
+    ldnt(m, j1, mm[1]); ldnt(v, j1, vv[1]);
+    const float4 pq = ((float4*)p)[j1];
+    pp[0][0] = pa.x; pp[0][1] = pa.y; pp[0][2] = pa.z; pp[0][3] = pa.w;
+    pp[1][0] = pq.x; pp[1][1] = pq.y; pp[1][2] = pq.z; pp[1][3] = pq.w;
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        mm[u][e] = b1 * mm[u][e] + (1.f - b1) * gg[u][e];
-        vv[u][e] = b2 * vv[u][e] + (1.f - b2) * gg[u][e] * gg[u][e];
-        const float denom = sqrtf(vv[u][e]) / bc2_sqrt + eps;
-        pp[u][e] -= a * (mm[u][e] / denom);
-      }
-    stnt(m, i0, mm[0][0], mm[0][1], mm[0][2], mm[0][3]);
-    stnt(v, i0, vv[0][0], vv[0][1], vv[0][2], vv[0][3]);
-    ((float4*)p)[i0] = make_float4(pp[0][0], pp[0][1], pp[0][2], pp[0][3]);
-    if (pb) ((uint2*)pb)[i0] = make_uint2(pack2_bf16(pp[0][0], pp[0][1]), pack2_bf16(pp[0][2], pp[0][3]));
-    if (two) {
-      stnt(m, i1, mm[1][0], mm[1][1], mm[1][2], mm[1][3]);
-      stnt(v, i1, vv[1][0], vv[1][1], vv[1][2], vv[1][3]);
-      ((float4*)p)[i1] = make_float4(pp[1][0], pp[1][1], pp[1][2], pp[1][3]);
-      if (pb) ((uint2*)pb)[i1] = make_uint2(pack2_bf16(pp[1][0], pp[1][1]), pack2_bf16(pp[1][2], pp[1][3]));
-    }
+      for (int e = 0; e < 4; ++e)
+        adam_update<DECAY>(gg[u][e], pp[u][e], mm[u][e], vv[u][e], grad_scale, coef, wd, shrink, a, b1, b2, eps,
+                           bc2_sqrt);
+    put(i0, mm[0], vv[0], pp[0]);
+    if (two) put(i1, mm[1], vv[1], pp[1]);
   }
   // scalar tail (n not a multiple of 4, or unaligned buffers: then n4 == 0 and this is everything)
-  for (long long i = n4 * 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long long)gridDim.x * blockDim.x) {
-    const float gi = (G16 ? bf16_to_f32(gh[i]) : g[i]) * grad_scale;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+  for (long long i = n4 * 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    float pi = p[i], mi = m[i], vi = v[i];
+    adam_update<DECAY>(G16 ? bf16_to_f32(gh[i]) : g[i], pi, mi, vi, grad_scale, coef, wd, shrink, a, b1, b2, eps,
+                       bc2_sqrt);
     m[i] = mi;
     v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    const float pi = p[i] - a * (mi / denom);
     p[i] = pi;
     if (pb) pb[i] = f32_to_bf16(pi);
   }
 }
 
-static int adam_dev_launch(float* p, const void* g, bool g16, float* m, float* v, void* p_bf16, int64_t n,
-                           float lr, float beta1, float beta2, float eps, int* step_counter,
-                           float grad_scale, void* stream, bool tick = true) {
-  const bool aligned = (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) == 0 &&
-                       (((uintptr_t)g) & (g16 ? 7 : 15)) == 0 && (((uintptr_t)p_bf16) & 7) == 0;
-  const long long n4 = aligned ? n / 4 : 0;
-  long long grid = ((aligned ? n4 : (long long)n) + 255) / 256;
-  if (grid > 4096) grid = 4096;
-  if (grid < 1) grid = 1;
-  if (tick) hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_counter);
-  if (g16)
-    hipLaunchKernelGGL(adam_dev_kernel<true>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m,
-                       v, (uint16_t*)p_bf16, n4, (long long)n, lr, beta1, beta2, eps,
-                       (const int*)step_counter, grad_scale);
-  else
-    hipLaunchKernelGGL(adam_dev_kernel<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m,
-                       v, (uint16_t*)p_bf16, n4, (long long)n, lr, beta1, beta2, eps,
-                       (const int*)step_counter, grad_scale);
-  VS_CHECK_LAUNCH();
-  return VS_OK;
-}
-
-extern "C" int vs_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, float lr,
-                                float beta1, float beta2, float eps, int* step_counter,
-                                float grad_scale, void* stream) {
-  VS_CHECK_ARG(p && g && m && v && n > 0 && step_counter, "bad args");
-  return adam_dev_launch(p, g, false, m, v, nullptr, n, lr, beta1, beta2, eps, step_counter, grad_scale, stream);
-}
-
-extern "C" int vs_adam_step_dev_cast(float* p, const float* g, float* m, float* v, void* p_bf16,
-                                     int64_t n, float lr, float beta1, float beta2, float eps,
-                                     int* step_counter, float grad_scale, void* stream) {
-  VS_CHECK_ARG(p && g && m && v && p_bf16 && n > 0 && step_counter, "bad args");
-  return adam_dev_launch(p, g, false, m, v, p_bf16, n, lr, beta1, beta2, eps, step_counter, grad_scale, stream);
-}
-
-extern "C" int vs_adam_step_dev_cast_g16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16,
-                                         int64_t n, float lr, float beta1, float beta2, float eps,
-                                         int* step_counter, float grad_scale, void* stream) {
-  VS_CHECK_ARG(p && g_bf16 && m && v && p_bf16 && n > 0 && step_counter, "bad args");
-  return adam_dev_launch(p, g_bf16, true, m, v, p_bf16, n, lr, beta1, beta2, eps, step_counter, grad_scale,
-                         stream);
-}
-
-extern "C" int vs_adam_tick(int* step_counter, void* stream) {
-  VS_CHECK_ARG(step_counter, "null counter");
-  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_counter);
-  VS_CHECK_LAUNCH();
-  return VS_OK;
-}
-
-extern "C" int vs_adam_step_dev_range(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16,
-                                      int64_t n, float lr, float beta1, float beta2, float eps,
-                                      const int* step_counter, float grad_scale, void* stream) {
-  VS_CHECK_ARG(p && g && m && v && n > 0 && step_counter, "bad args");
-  return adam_dev_launch(p, g, g_is_bf16 != 0, m, v, p_bf16, n, lr, beta1, beta2, eps, (int*)step_counter,
-                         grad_scale, stream, false);
+// The rate as a launch argument -- fixed once the launch is captured; no decay, no clip (coef 1.0f folds away).
+template <bool G16>
+__global__ void adam_dev_kernel(float* p, const void* gv, float* m, float* v, uint16_t* pb,
+                                long long n4, long long n, float lr, float b1, float b2, float eps,
+                                const int* step, float grad_scale) {
+  const float t = (float)step[0];
+  const float bc1 = 1.f - powf(b1, t);
+  const float bc2_sqrt = sqrtf(1.f - powf(b2, t));
+  const float a = lr / bc1;
+  adam_body<G16, 0>(p, gv, m, v, pb, n4, n, lr, 0.f, a, b1, b2, eps, bc2_sqrt, grad_scale, 1.f);
 }
 
 // ----------------------------------------------------------------------------
@@ -1735,9 +1693,7 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const void* gv, long lo
     auto group = [&](long long j, double s) __attribute__((always_inline)) {
       float x[4];
       if (G16) {
-        const uint2 w = ((const uint2*)(gh + head))[j];
-        x[0] = __uint_as_float(w.x << 16); x[1] = __uint_as_float(w.x & 0xffff0000u);
-        x[2] = __uint_as_float(w.y << 16); x[3] = __uint_as_float(w.y & 0xffff0000u);
+        bf16x4_to_f32(((const uint2*)(gh + head))[j], x);
       } else {
         const float4 w = ((const float4*)(g + head))[j];
         x[0] = w.x; x[1] = w.y; x[2] = w.z; x[3] = w.w;
@@ -1783,94 +1739,6 @@ extern "C" int vs_grad_sumsq(const void* g, int g_is_bf16, int64_t n, void* work
   return VS_OK;
 }
 
-// adam_dev_kernel's loops with the clip coefficient and one of three decay forms compiled in.  DECAY 0: none -- the
-// arithmetic per element is adam_dev_kernel's, and with coef == 1.0f so are the bits; 1: torch.optim.Adam's L2 form,
-// g += wd * p after the clip; 2: AdamW's, p *= 1 - lr * wd before the update.
-template <bool G16, int DECAY>
-__device__ __forceinline__ void adam_hp_body(float* p, const void* gv, float* m, float* v, uint16_t* pb, long long n4,
-                                             long long n, float lr, float wd, float a, float b1, float b2, float eps,
-                                             float bc2_sqrt, float grad_scale, float coef) {
-  const float* g = (const float*)gv;
-  const uint16_t* gh = (const uint16_t*)gv;
-  const float shrink = 1.f - lr * wd;
-  typedef __attribute__((ext_vector_type(4))) float nt_f4;
-  typedef __attribute__((ext_vector_type(2))) unsigned nt_u2;
-  auto ldnt = [](const float* q, long long i) __attribute__((always_inline)) {
-    const nt_f4 t = __builtin_nontemporal_load((const nt_f4*)q + i);
-    return make_float4(t[0], t[1], t[2], t[3]);
-  };
-  auto stnt = [](float* q, long long i, float a0, float a1, float a2, float a3) __attribute__((always_inline)) {
-    const nt_f4 t = {a0, a1, a2, a3};
-    __builtin_nontemporal_store(t, (nt_f4*)q + i);
-  };
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x; i0 < n4; i0 += 2 * stride) {
-    const long long i1 = i0 + stride;
-    const bool two = i1 < n4;
-    const long long j1 = two ? i1 : i0;
-    float gg[2][4];
-    if (G16) {
-      const nt_u2 ga_ = __builtin_nontemporal_load((const nt_u2*)gv + i0), gb_ = __builtin_nontemporal_load((const nt_u2*)gv + j1);
-      const uint2 ga = make_uint2(ga_[0], ga_[1]), gb = make_uint2(gb_[0], gb_[1]);
-      gg[0][0] = __uint_as_float(ga.x << 16) * grad_scale;
-      gg[0][1] = __uint_as_float(ga.x & 0xffff0000u) * grad_scale;
-      gg[0][2] = __uint_as_float(ga.y << 16) * grad_scale;
-      gg[0][3] = __uint_as_float(ga.y & 0xffff0000u) * grad_scale;
-      gg[1][0] = __uint_as_float(gb.x << 16) * grad_scale;
-      gg[1][1] = __uint_as_float(gb.x & 0xffff0000u) * grad_scale;
-      gg[1][2] = __uint_as_float(gb.y << 16) * grad_scale;
-      gg[1][3] = __uint_as_float(gb.y & 0xffff0000u) * grad_scale;
-    } else {
-      const float4 ga = ldnt((const float*)gv, i0), gb = ldnt((const float*)gv, j1);
-      gg[0][0] = ga.x * grad_scale; gg[0][1] = ga.y * grad_scale; gg[0][2] = ga.z * grad_scale; gg[0][3] = ga.w * grad_scale;
-      gg[1][0] = gb.x * grad_scale; gg[1][1] = gb.y * grad_scale; gg[1][2] = gb.z * grad_scale; gg[1][3] = gb.w * grad_scale;
-    }
-    const float4 ma = ldnt(m, i0), va = ldnt(v, i0), pa = ((float4*)p)[i0];
-    const float4 mb = ldnt(m, j1), vb = ldnt(v, j1), pq = ((float4*)p)[j1];
-    float mm[2][4] = {{ma.x, ma.y, ma.z, ma.w}, {mb.x, mb.y, mb.z, mb.w}};
-    float vv[2][4] = {{va.x, va.y, va.z, va.w}, {vb.x, vb.y, vb.z, vb.w}};
-    float pp[2][4] = {{pa.x, pa.y, pa.z, pa.w}, {pq.x, pq.y, pq.z, pq.w}};
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        gg[u][e] = gg[u][e] * coef;
-        if (DECAY == 1) gg[u][e] += wd * pp[u][e];
-        if (DECAY == 2) pp[u][e] *= shrink;
-        mm[u][e] = b1 * mm[u][e] + (1.f - b1) * gg[u][e];
-        vv[u][e] = b2 * vv[u][e] + (1.f - b2) * gg[u][e] * gg[u][e];
-        const float denom = sqrtf(vv[u][e]) / bc2_sqrt + eps;
-        pp[u][e] -= a * (mm[u][e] / denom);
-      }
-    stnt(m, i0, mm[0][0], mm[0][1], mm[0][2], mm[0][3]);
-    stnt(v, i0, vv[0][0], vv[0][1], vv[0][2], vv[0][3]);
-    ((float4*)p)[i0] = make_float4(pp[0][0], pp[0][1], pp[0][2], pp[0][3]);
-    if (pb) ((uint2*)pb)[i0] = make_uint2(pack2_bf16(pp[0][0], pp[0][1]), pack2_bf16(pp[0][2], pp[0][3]));
-    if (two) {
-      stnt(m, i1, mm[1][0], mm[1][1], mm[1][2], mm[1][3]);
-      stnt(v, i1, vv[1][0], vv[1][1], vv[1][2], vv[1][3]);
-      ((float4*)p)[i1] = make_float4(pp[1][0], pp[1][1], pp[1][2], pp[1][3]);
-      if (pb) ((uint2*)pb)[i1] = make_uint2(pack2_bf16(pp[1][0], pp[1][1]), pack2_bf16(pp[1][2], pp[1][3]));
-    }
-  }
-  // scalar tail (n not a multiple of 4, or unaligned buffers: then n4 == 0 and this is everything)
-  for (long long i = n4 * 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long long)gridDim.x * blockDim.x) {
-    float gi = ((G16 ? bf16_to_f32(gh[i]) : g[i]) * grad_scale) * coef;
-    float pi = p[i];
-    if (DECAY == 1) gi += wd * pi;
-    if (DECAY == 2) pi *= shrink;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi = pi - a * (mi / denom);
-    p[i] = pi;
-    if (pb) pb[i] = f32_to_bf16(pi);
-  }
-}
-
 template <bool G16>
 __global__ __launch_bounds__(256) void adam_hp_kernel(float* p, const void* gv, float* m, float* v, uint16_t* pb,
                                                       long long n4, long long n, float* hyper, float b1, float b2,
@@ -1894,19 +1762,19 @@ __global__ __launch_bounds__(256) void adam_hp_kernel(float* p, const void* gv, 
   const float bc2_sqrt = sqrtf(1.f - powf(b2, t));
   const float a = lr / bc1;
   if (wd == 0.f)
-    adam_hp_body<G16, 0>(p, gv, m, v, pb, n4, n, lr, wd, a, b1, b2, eps, bc2_sqrt, grad_scale, coef);
+    adam_body<G16, 0>(p, gv, m, v, pb, n4, n, lr, wd, a, b1, b2, eps, bc2_sqrt, grad_scale, coef);
   else if (flags & 1)
-    adam_hp_body<G16, 2>(p, gv, m, v, pb, n4, n, lr, wd, a, b1, b2, eps, bc2_sqrt, grad_scale, coef);
+    adam_body<G16, 2>(p, gv, m, v, pb, n4, n, lr, wd, a, b1, b2, eps, bc2_sqrt, grad_scale, coef);
   else
-    adam_hp_body<G16, 1>(p, gv, m, v, pb, n4, n, lr, wd, a, b1, b2, eps, bc2_sqrt, grad_scale, coef);
+    adam_body<G16, 1>(p, gv, m, v, pb, n4, n, lr, wd, a, b1, b2, eps, bc2_sqrt, grad_scale, coef);
 }
 
-extern "C" int vs_adam_step_hp(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16, int64_t n,
-                               float* hyper, float beta1, float beta2, float eps, int* step_counter, int tick,
-                               float grad_scale, int flags, const void* sumsq_ws, void* stream) {
-  VS_CHECK_ARG(p && g && m && v && n > 0 && hyper && step_counter, "bad args");
-  VS_CHECK_ARG((flags & ~1) == 0 && (((uintptr_t)sumsq_ws) & 7) == 0, "unknown flag bits, or a misaligned sum-of-squares workspace");
-  const bool g16 = g_is_bf16 != 0;
+// The launch behind every vs_adam_step_* entry point below: float4 groups when every buffer is aligned for them
+// (otherwise n4 == 0 and the scalar tail does everything), the optional tick, then adam_hp_kernel when `hyper` is
+// given and adam_dev_kernel with the rate `lr` otherwise.
+static int adam_launch(float* p, const void* g, bool g16, float* m, float* v, void* p_bf16, int64_t n, float lr,
+                       float* hyper, float beta1, float beta2, float eps, int* step_counter, bool tick,
+                       float grad_scale, int flags, const void* sumsq_ws, void* stream) {
   const bool aligned = (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) == 0 &&
                        (((uintptr_t)g) & (g16 ? 7 : 15)) == 0 && (((uintptr_t)p_bf16) & 7) == 0;
   const long long n4 = aligned ? n / 4 : 0;
@@ -1914,16 +1782,67 @@ extern "C" int vs_adam_step_hp(float* p, const void* g, int g_is_bf16, float* m,
   if (grid > 4096) grid = 4096;
   if (grid < 1) grid = 1;
   if (tick) hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_counter);
-  if (g16)
-    hipLaunchKernelGGL(adam_hp_kernel<true>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+  if (hyper) {
+    const auto kernel = g16 ? adam_hp_kernel<true> : adam_hp_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
                        (uint16_t*)p_bf16, n4, (long long)n, hyper, beta1, beta2, eps, (const int*)step_counter,
                        grad_scale, flags, (const double*)sumsq_ws);
-  else
-    hipLaunchKernelGGL(adam_hp_kernel<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                       (uint16_t*)p_bf16, n4, (long long)n, hyper, beta1, beta2, eps, (const int*)step_counter,
-                       grad_scale, flags, (const double*)sumsq_ws);
+  } else {
+    const auto kernel = g16 ? adam_dev_kernel<true> : adam_dev_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                       (uint16_t*)p_bf16, n4, (long long)n, lr, beta1, beta2, eps, (const int*)step_counter,
+                       grad_scale);
+  }
   VS_CHECK_LAUNCH();
   return VS_OK;
+}
+
+extern "C" int vs_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, float lr,
+                                float beta1, float beta2, float eps, int* step_counter,
+                                float grad_scale, void* stream) {
+  VS_CHECK_ARG(p && g && m && v && n > 0 && step_counter, "bad args");
+  return adam_launch(p, g, false, m, v, nullptr, n, lr, nullptr, beta1, beta2, eps, step_counter, true, grad_scale, 0,
+                     nullptr, stream);
+}
+
+extern "C" int vs_adam_step_dev_cast(float* p, const float* g, float* m, float* v, void* p_bf16,
+                                     int64_t n, float lr, float beta1, float beta2, float eps,
+                                     int* step_counter, float grad_scale, void* stream) {
+  VS_CHECK_ARG(p && g && m && v && p_bf16 && n > 0 && step_counter, "bad args");
+  return adam_launch(p, g, false, m, v, p_bf16, n, lr, nullptr, beta1, beta2, eps, step_counter, true, grad_scale, 0,
+                     nullptr, stream);
+}
+
+extern "C" int vs_adam_step_dev_cast_g16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16,
+                                         int64_t n, float lr, float beta1, float beta2, float eps,
+                                         int* step_counter, float grad_scale, void* stream) {
+  VS_CHECK_ARG(p && g_bf16 && m && v && p_bf16 && n > 0 && step_counter, "bad args");
+  return adam_launch(p, g_bf16, true, m, v, p_bf16, n, lr, nullptr, beta1, beta2, eps, step_counter, true, grad_scale,
+                     0, nullptr, stream);
+}
+
+extern "C" int vs_adam_tick(int* step_counter, void* stream) {
+  VS_CHECK_ARG(step_counter, "null counter");
+  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_counter);
+  VS_CHECK_LAUNCH();
+  return VS_OK;
+}
+
+extern "C" int vs_adam_step_dev_range(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16,
+                                      int64_t n, float lr, float beta1, float beta2, float eps,
+                                      const int* step_counter, float grad_scale, void* stream) {
+  VS_CHECK_ARG(p && g && m && v && n > 0 && step_counter, "bad args");
+  return adam_launch(p, g, g_is_bf16 != 0, m, v, p_bf16, n, lr, nullptr, beta1, beta2, eps, (int*)step_counter, false,
+                     grad_scale, 0, nullptr, stream);
+}
+
+extern "C" int vs_adam_step_hp(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16, int64_t n,
+                               float* hyper, float beta1, float beta2, float eps, int* step_counter, int tick,
+                               float grad_scale, int flags, const void* sumsq_ws, void* stream) {
+  VS_CHECK_ARG(p && g && m && v && n > 0 && hyper && step_counter, "bad args");
+  VS_CHECK_ARG((flags & ~1) == 0 && (((uintptr_t)sumsq_ws) & 7) == 0, "unknown flag bits, or a misaligned sum-of-squares workspace");
+  return adam_launch(p, g, g_is_bf16 != 0, m, v, p_bf16, n, 0.f, hyper, beta1, beta2, eps, step_counter, tick != 0,
+                     grad_scale, flags, sumsq_ws, stream);
 }
 
 __global__ void cast_f32_bf16_kernel(const float* x, uint16_t* y, long long n) {

@@ -6,9 +6,14 @@ all-reduce of ~39 M gradient elements, plus a BN-buffer broadcast and
 (`main_dist.py:50`).  Here every parameter and every gradient is a view into ONE
 fp32 buffer each, so a step is: zero the gradient arena (one memset) ->
 forward/backward (HIP kernels write gradients in place) -> ONE all-reduce over
-RCCL (`torch.distributed`, backend "nccl") -> ONE fused Adam launch
-(`vs_adam_step`, the 1/world_size averaging folded in) -> refresh the bf16
-kernel-layout weight copies.  No unused parameters exist (the upstream 2304->400
+RCCL (`torch.distributed`, backend "nccl") -> ONE fused Adam launch (the
+1/world_size averaging and the bf16 weight cast folded in) -> refresh the
+transposed kernel-layout weight copies.  The launch is `vs_adam_step_dev_cast`
+(`_dev_cast_g16` on bf16 gradients, `_dev` for an arena without a bf16 copy);
+`vs_adam_step_hp`, behind `vs_grad_sumsq` when it clips, once a setting keeps the
+hyper-parameters in device memory; and per gradient bucket `vs_adam_tick` once,
+then `vs_adam_step_dev_range` or `vs_adam_step_hp` for every range.  All of them
+run one kernel body.  No unused parameters exist (the upstream 2304->400
 head is never built) and BN running statistics are not re-broadcast (SURVEY.md
 section 5: rank 0's are the ones checkpointed).
 """
@@ -502,63 +507,51 @@ class ArenaAdam:
             a = self.arena
             ops.grad_sumsq(a.grad16 if grad_bf16 else a.grad, self.sumsq_ws)
 
+    def _update(self, lo, hi, world, grad_bf16, tick):
+        """The update of arena elements [lo, hi): one `ops` call on views of the parameters, the gradients, both
+        moments and the bf16 copy.  tick: the launch also advances the step count (a whole step); otherwise `tick()`
+        has.  On the device-side path the norm pass comes first: with every ticking call, and before the first range
+        after a `tick()`."""
+        a = self.arena
+        p, m, v = a.data[lo:hi], self.m[lo:hi], self.v[lo:hi]
+        g = (a.grad16 if grad_bf16 else a.grad)[lo:hi]
+        pb = a.data_bf16[lo:hi] if a.data_bf16 is not None else None
+        (b1, b2), scale = self.betas, 1.0 / world
+        if self.hyper is not None:
+            if tick or self._norm_due:
+                self._norm_pass(grad_bf16)
+            if not tick:
+                self._norm_due = False
+            ops.adam_step_hp(p, g, m, v, pb, self.hyper, b1, b2, self.eps, self.t, tick=tick, grad_scale=scale,
+                             decoupled=self.decoupled_weight_decay, sumsq_ws=self.sumsq_ws)
+        elif not tick:
+            ops.adam_step_dev_range(p, g, m, v, pb, self.lr, b1, b2, self.eps, self.t, grad_scale=scale)
+        elif pb is None:
+            ops.adam_step_dev(p, g, m, v, self.lr, b1, b2, self.eps, self.t, grad_scale=scale)
+        elif grad_bf16:
+            ops.adam_step_dev_cast_g16(p, g, m, v, pb, self.lr, b1, b2, self.eps, self.t, grad_scale=scale)
+        else:
+            ops.adam_step_dev_cast(p, g, m, v, pb, self.lr, b1, b2, self.eps, self.t, grad_scale=scale)
+
     def step_range(self, lo, hi, world=1, grad_bf16=False):
         """The update of arena elements [lo, hi) against the count `tick()` set; no refresh of derived weight
         images (the caller runs `finish_ranged()` once every range is done).  With `max_grad_norm` the first range
         after `tick()` runs the norm pass over the WHOLE arena: every gradient has to be final by then."""
-        a = self.arena
-        if hi <= lo:
-            return
-        g = (a.grad16 if grad_bf16 else a.grad)[lo:hi]
-        pb = a.data_bf16[lo:hi] if a.data_bf16 is not None else None
-        if self.hyper is not None:
-            if self._norm_due:
-                self._norm_pass(grad_bf16)
-                self._norm_due = False
-            ops.adam_step_hp(a.data[lo:hi], g, self.m[lo:hi], self.v[lo:hi], pb, self.hyper, self.betas[0],
-                             self.betas[1], self.eps, self.t, tick=False, grad_scale=1.0 / world,
-                             decoupled=self.decoupled_weight_decay, sumsq_ws=self.sumsq_ws)
-            return
-        ops.adam_step_dev_range(a.data[lo:hi], g, self.m[lo:hi], self.v[lo:hi], pb, self.lr, self.betas[0],
-                                self.betas[1], self.eps, self.t, grad_scale=1.0 / world)
+        if hi > lo:
+            self._update(lo, hi, world, grad_bf16, tick=False)
 
     def finish_ranged(self, defer_transposes=False):
-        a = self.arena
-        if a.data_bf16 is not None:
-            a.refresh(cast=False, transposes=not defer_transposes)
-        else:
-            a.refresh()
+        """Refresh the derived weight images.  No cast: an arena that keeps a bf16 copy had it written by the update,
+        and one that keeps none has no images to refresh."""
+        self.arena.refresh(cast=False, transposes=not defer_transposes)
 
     def step(self, world=1, defer_transposes=False, grad_bf16=False):
         """defer_transposes: leave the dgrad weight images stale; the caller refreshes them with
         `arena.transposes_async()` at the start of the next step (bench.py).
         grad_bf16: the (all-reduced) gradients are read from the bf16 arena `arena.grad16`."""
         a = self.arena
-        if self.hyper is not None:
-            if a.data_bf16 is None and grad_bf16:
-                a.unpack_grad_bf16(0, a.numel)
-                grad_bf16 = False
-            self._norm_pass(grad_bf16)
-            ops.adam_step_hp(a.data, a.grad16 if grad_bf16 else a.grad, self.m, self.v, a.data_bf16, self.hyper,
-                             self.betas[0], self.betas[1], self.eps, self.t, tick=True, grad_scale=1.0 / world,
-                             decoupled=self.decoupled_weight_decay, sumsq_ws=self.sumsq_ws)
-            if a.data_bf16 is not None:
-                a.refresh(cast=False, transposes=not defer_transposes)
-            else:
-                a.refresh()
-            return
-        if a.data_bf16 is not None:
-            if grad_bf16:
-                ops.adam_step_dev_cast_g16(a.data, a.grad16, self.m, self.v, a.data_bf16, self.lr,
-                                           self.betas[0], self.betas[1], self.eps, self.t,
-                                           grad_scale=1.0 / world)
-            else:
-                ops.adam_step_dev_cast(a.data, a.grad, self.m, self.v, a.data_bf16, self.lr, self.betas[0],
-                                       self.betas[1], self.eps, self.t, grad_scale=1.0 / world)
-            a.refresh(cast=False, transposes=not defer_transposes)
-        else:
-            if grad_bf16:
-                a.unpack_grad_bf16(0, a.numel)
-            ops.adam_step_dev(a.data, a.grad, self.m, self.v, self.lr, self.betas[0], self.betas[1],
-                              self.eps, self.t, grad_scale=1.0 / world)
-            a.refresh()
+        if a.data_bf16 is None and grad_bf16:
+            a.unpack_grad_bf16(0, a.numel)
+            grad_bf16 = False
+        self._update(0, a.numel, world, grad_bf16, tick=True)
+        self.finish_ranged(defer_transposes)

@@ -693,6 +693,33 @@ int vs_embed_scatter_bwd(const int64_t* tokens, const float* dx, float* demb, in
                          int64_t pad, void* stream);
 int vs_relu_bwd(const float* dy, const float* y, float* dx, int64_t n, void* stream);
 
+/* ---- RoBERTa encoder (event-relation task; transformers 3.3.1 modeling_roberta), csrc/roberta_ops.hip, fp32.
+ * Bidirectional self-attention on the fused projection output qkv[R,L,3D]: s_ij = q_i.k_j / sqrt(dh) +
+ * (1 - key_mask[r,j]) * -1e4, softmax over all L keys, out[R,L,D] = p.v with the heads merged; key_mask u8 [R,L]
+ * (1 = attend) or NULL; queries at padded positions are computed like any other.  The mask term is evaluated without its
+ * fp32 rounding: beside a valid key a masked key weighs exactly 0, a sequence whose mask is all zero runs unmasked (the
+ * formula's value for |s| < 9e3).  Both products run on
+ * v_mfma_f32_16x16x4_f32 (exact fp32); K and V of a head are LDS-resident, so dh is 16, 32, 64 or 128 and L is bounded
+ * by the 160 KiB of LDS (dh = 64: L <= 192 forward, L <= 144 backward); a shape outside returns VS_ERR_BAD_ARG
+ * and launches nothing. */
+int vs_attn_pad_fwd(const float* qkv, const uint8_t* key_mask, float* out, int R, int L, int H, int dh, void* stream);
+/* Backward of vs_attn_pad_fwd: dqkv[R,L,3D] from dout[R,L,D]; p is recomputed (dV = P^T dO, dS = P * (dO V^T -
+ * rowsum(P * dO V^T)), dQ = dS K / sqrt(dh), dK = dS^T Q / sqrt(dh)); scratch of vs_attn_pad_bwd_scratch_bytes(R,L,H)
+ * bytes carries p and dS between the two launches; no atomics, fixed summation order. */
+size_t vs_attn_pad_bwd_scratch_bytes(int R, int L, int H);
+int vs_attn_pad_bwd(const float* qkv, const uint8_t* key_mask, const float* dout, float* dqkv, void* scratch,
+                    size_t scratch_bytes, int R, int L, int H, int dh, void* stream);
+/* RobertaEmbeddings before its LayerNorm: pos_ids_out[r,l] = cumsum(tokens != pad)[l] * (tokens[l] != pad) + pad
+ * (from the token ids, not from the attention mask), out[r,l,:] = word[tokens] + pos[pos_id] + type0 (the single
+ * token-type row).  Refuses L + pad + 1 > n_pos; D % 4 == 0; token ids must index the word table. */
+int vs_roberta_embed(const int64_t* tokens, const float* word, const float* pos, const float* type0, float* out,
+                     int64_t* pos_ids_out, int R, int L, int D, int pad, int n_pos, void* stream);
+/* Exact (erf) GELU and tanh with their backwards (x_pre: the GELU's input; y: the tanh's output). */
+int vs_gelu_erf_fwd(const float* x, float* y, int64_t n, void* stream);
+int vs_gelu_erf_bwd(const float* dy, const float* x_pre, float* dx, int64_t n, void* stream);
+int vs_tanh_fwd(const float* x, float* y, int64_t n, void* stream);
+int vs_tanh_bwd(const float* dy, const float* y, float* dx, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

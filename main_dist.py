@@ -29,7 +29,8 @@ Ranks: the reference spawns them from a parent that has touched CUDA (`mp.spawn`
 GPU (`vidsitu_amd/dist_launch.py`), rendezvous on 127.0.0.1 at a free port (the reference hard-codes 9997,
 `utils/trn_dist_utils.py:30`, so two jobs on one node collide).  Under `torch.distributed.run` (RANK /
 WORLD_SIZE already set) the process is a rank and spawns nothing.
-`task_type=vb_arg` rows train on the SRL batch contract (`synth_data.synth_srl_batch`).  An empty
+`task_type=vb_arg` rows train on the SRL batch contract (`synth_data.synth_srl_batch`), `task_type=evrel` rows on
+the event-relation contract (`synth_data.synth_evrel_batch`; `--mdl.rob_mdl_name=roberta-synth-tiny` for a small encoder).  An empty
 `train.resume_path` means `<tmp_path>/models/<uid>.pth`, as `Learner.load_model_dict` does
 (`utils/trn_utils.py:643-646`).
 Not kept: MLflow / progress bars / per-epoch checkpoint rotation (`utils/trn_utils.py`, out of scope).
@@ -135,6 +136,11 @@ def main_fn(rank, cfg, steps, graph=True, val_every=0):
 
         batches = [synth_data.synth_srl_batch(comm, bs, n_ev, feat_dim=get_head_dim(cfg),
                                               seed=cfg.synth.seed + 17 * i + rank, device=dev) for i in range(nb)]
+    elif cfg.task_type == "evrel":  # event relations: roberta token sequences + pre-extracted features
+        from vidsitu_amd.mdl_sf_base import get_head_dim
+
+        batches = [synth_data.synth_evrel_batch(comm, bs, n_ann=1, feat_dim=get_head_dim(cfg),
+                                                seed=cfg.synth.seed + 17 * i + rank, device=dev) for i in range(nb)]
     else:
         batches = [synth_data.synth_batch(cfg, comm, bs, n_ev, seed=cfg.synth.seed + 17 * i + rank, device=dev)
                    for i in range(nb)]
@@ -203,8 +209,8 @@ def main_dist(uid, **kwargs):
     graph = kwargs.pop("graph", None)
     val_every = int(kwargs.pop("val_every", 0))
     cfg = get_cfg(kwargs)
-    # hipGraph replay is the default for the verb-prediction rows (the measured step); the SRL rows (`vb_arg`) keep an
-    # eager TrainStep unless --graph=1 asks for a capture (which raises if the model syncs with the host)
+    # hipGraph replay is the default for the verb-prediction rows (the measured step); the SRL and event-relation rows (`vb_arg`, `evrel`) keep
+    # an eager TrainStep unless --graph=1 asks for a capture (which raises if the model syncs with the host)
     graph = (cfg.task_type == "vb") if graph is None else str(graph) not in ("0", "false", "False")
     cfg.uid = uid
     n = dist_launch.visible_gpus()  # counts devices, does not initialise one

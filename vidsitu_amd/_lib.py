@@ -200,6 +200,14 @@ SIGNATURES = {
     "vs_gpt2_embed_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "vs_xent_ignore_grad": (_i, [_p, _p, _p, _p, _i, _i, _i64, _i, _f, _p]),
     "vs_xent_ignore_grad_dev": (_i, [_p, _p, _p, _p, _i, _i, _i64, _i, _p, _p]),
+    "vs_attn_pad_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "vs_attn_pad_bwd_scratch_bytes": (_sz, [_i, _i, _i]),
+    "vs_attn_pad_bwd": (_i, [_p, _p, _p, _p, _p, _sz, _i, _i, _i, _i, _p]),
+    "vs_roberta_embed": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "vs_gelu_erf_fwd": (_i, [_p, _p, _i64, _p]),
+    "vs_gelu_erf_bwd": (_i, [_p, _p, _p, _i64, _p]),
+    "vs_tanh_fwd": (_i, [_p, _p, _i64, _p]),
+    "vs_tanh_bwd": (_i, [_p, _p, _p, _i64, _p]),
 }
 
 

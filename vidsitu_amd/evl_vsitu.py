@@ -106,3 +106,52 @@ class EvalB_Gen(EvalB):
                                               "text": wvoc.decode(ev_sent[0], skip_special_tokens=True)}
             out.append({"ann_idx": ann_idx, "vb_output": vb_output})
         return out
+
+
+class EvalB_Acc(EvalB):
+    """`EvalB_Acc` (`vidsitu_code/evl_vsitu.py:217-261`), the event-relation rows' evaluation: per video the most
+    probable relation of every (event pair, annotation) and its probability, from `vs_softmax_topk(k=1)`.  The
+    metrics over the annotation files (`EvlFn_EvRel.simple_acc_evrel`: majority vote over annotators, the evaluation
+    mask) are out of scope as for `EvalB`; `forward` scores the batches' own labels."""
+
+    def __init__(self, cfg, comm, device=None):
+        super().__init__(cfg, comm, device)
+        self.met_keys = ["Macro_Top_1", "Top_1"]
+        self.compute_loss = True
+
+    @torch.no_grad()
+    def forward_one_batch(self, mdl, inp):
+        mdl_out = mdl(inp)["mdl_out"]  # [B, 4, n_ann, 5]
+        B, E, A, V = mdl_out.shape
+        assert E == 4
+        probs, idx = ops.softmax_topk(mdl_out.reshape(B * E * A, V).float(), 1)
+        probs = probs.view(B, E, A).tolist()
+        idx = idx.view(B, E, A).tolist()
+        names = self.comm.evrel_dct_opp
+        return [{"pred_evrels_ev": [[names[i] for i in ev] for ev in idx[b]],
+                 "pred_scores_ev": probs[b],
+                 "ann_idx": ann_idx} for b, ann_idx in enumerate(inp["vseg_idx"].tolist())]
+
+    @torch.no_grad()
+    def forward(self, model, loss_fn, dl, dl_name="valid", rank=0, pred_path=None, mb=None):
+        """Mean loss, and over the batches' labels: `Top_1` (fraction of relations predicted right) and `Macro_Top_1`
+        (the mean of that fraction per relation class that occurs, `evl_fns.py:183-194`)."""
+        model.eval()
+        loss_sum, nb = 0.0, 0
+        hit_by_cls, n_by_cls = {}, {}
+        for batch in dl:
+            out = model(batch)
+            loss_sum += float(loss_fn(out, batch)["loss"])
+            nb += 1
+            V = out["mdl_out"].shape[-1]
+            _, idx = ops.softmax_topk(out["mdl_out"].reshape(-1, V).float(), 1)
+            lab = batch["evrel_labs"].reshape(-1)
+            hit = idx[:, 0] == lab
+            for c in lab.unique().tolist():
+                sel = lab == c
+                n_by_cls[c] = n_by_cls.get(c, 0) + int(sel.sum())
+                hit_by_cls[c] = hit_by_cls.get(c, 0) + int(hit[sel].sum())
+        n = sum(n_by_cls.values())
+        macro = [hit_by_cls[c] / n_by_cls[c] for c in n_by_cls]
+        return ({"loss": loss_sum / max(nb, 1)},
+                {"Macro_Top_1": sum(macro) / max(len(macro), 1), "Top_1": sum(hit_by_cls.values()) / max(n, 1)})

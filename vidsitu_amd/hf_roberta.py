@@ -1,0 +1,387 @@
+"""RoBERTa encoder of the event-relation models (`vidsitu_code/mdl_evrel.py:21,62`) on the HIP kernels of
+csrc/roberta_ops.hip and the fp32 GEMM / LayerNorm kernels the GPT-2 path already uses.
+
+The reference builds `RobertaForSequenceClassification.from_pretrained(cfg.mdl.rob_mdl_name, num_labels=5)` and
+`RobertaModel.from_pretrained(..., add_pooling_layer=True)` (huggingface transformers==3.3.1); there is no network here,
+so `RobertaModelHip` / `RobertaForSequenceClassificationHip` are built from the architecture's dimensions with random
+weights and load a huggingface state dict when one is given (same keys and shapes; the `embeddings.position_ids` buffer
+that checkpoints of the pinned release carry is ignored).
+
+Semantics kept from the pinned release: additive key mask `(1 - attention_mask) * -1e4`, position ids from the token
+ids (`create_position_ids_from_input_ids`: padding tokens sit at `padding_idx`, the others count from `padding_idx + 1`),
+the single token-type row, post-LN residual blocks, erf GELU, LayerNorm eps 1e-5 (the checkpoints' value), pooler
+`tanh(dense(h[:, 0]))`, classification head `out_proj(tanh(dense(h[:, 0])))`.
+Stated difference: no dropout anywhere (as in the GPT-2 decoder of this package).
+
+Training: `forward_train` keeps the activations, `backward` is a manual HIP backward behind ONE autograd node
+(`roberta_apply`); parameter gradients are written with overwrite semantics.
+"""
+import torch
+from torch import nn
+
+from . import ops
+
+ROBERTA_DIMS = {
+    # name: dict(n_layer, d_model, n_head, n_positions, vocab, d_ffn, pad, eps)
+    "roberta-base": dict(n_layer=12, d_model=768, n_head=12, n_positions=514, vocab_size=50265, d_ffn=3072,
+                         pad_token_id=1, layer_norm_eps=1e-5),
+    "roberta-synth-tiny": dict(n_layer=2, d_model=64, n_head=2, n_positions=130, vocab_size=101, d_ffn=128,
+                               pad_token_id=1, layer_norm_eps=1e-5),  # tests / main_dist on synthetic data
+}
+
+
+class _RobertaHip(nn.Module):
+    """Parameters under huggingface's names (flat registration, '.' -> '__'), the encoder's forward / backward."""
+
+    PREFIX = ""
+
+    def __init__(self, n_layer, d_model, n_head, n_positions, vocab_size, d_ffn, pad_token_id=1, layer_norm_eps=1e-5,
+                 add_pooling_layer=True, num_labels=0):
+        super().__init__()
+        if d_model % n_head:
+            raise ValueError("d_model must be a multiple of n_head")
+        self.n_layer, self.d_model, self.n_head, self.n_positions = n_layer, d_model, n_head, n_positions
+        self.d_ffn, self.pad, self.eps = d_ffn, pad_token_id, layer_norm_eps
+        self.has_pooler, self.num_labels = bool(add_pooling_layer), int(num_labels)
+        self.config = type("Cfg", (), dict(num_hidden_layers=n_layer, hidden_size=d_model, num_attention_heads=n_head,
+                                           max_position_embeddings=n_positions, vocab_size=vocab_size,
+                                           intermediate_size=d_ffn, pad_token_id=pad_token_id,
+                                           layer_norm_eps=layer_norm_eps, type_vocab_size=1, num_labels=num_labels))()
+        p = {}
+        pre = self.PREFIX
+
+        def add(name, *shape, std=0.02, ones=False):
+            t = torch.ones(*shape) if ones else (torch.randn(*shape) * std if std else torch.zeros(*shape))
+            p[pre + name] = nn.Parameter(t)
+
+        def dense(name, n_out, n_in):
+            add(name + ".weight", n_out, n_in)
+            add(name + ".bias", n_out, std=0)
+
+        def lnorm(name):
+            add(name + ".weight", d_model, ones=True)
+            add(name + ".bias", d_model, std=0)
+
+        add("embeddings.word_embeddings.weight", vocab_size, d_model)
+        add("embeddings.position_embeddings.weight", n_positions, d_model)
+        add("embeddings.token_type_embeddings.weight", 1, d_model)
+        with torch.no_grad():  # nn.Embedding(padding_idx): the row starts at zero (and never receives a gradient)
+            p[pre + "embeddings.word_embeddings.weight"][pad_token_id].zero_()
+            p[pre + "embeddings.position_embeddings.weight"][pad_token_id].zero_()
+        lnorm("embeddings.LayerNorm")
+        for i in range(n_layer):
+            q = f"encoder.layer.{i}."
+            for s in ("query", "key", "value"):
+                dense(q + "attention.self." + s, d_model, d_model)
+            dense(q + "attention.output.dense", d_model, d_model)
+            lnorm(q + "attention.output.LayerNorm")
+            dense(q + "intermediate.dense", d_ffn, d_model)
+            dense(q + "output.dense", d_model, d_ffn)
+            lnorm(q + "output.LayerNorm")
+        if self.has_pooler:
+            dense("pooler.dense", d_model, d_model)
+        self._names = list(p)
+        if self.num_labels:  # RobertaClassificationHead lives beside the encoder, not under its prefix
+            for name, (n_out, n_in) in (("classifier.dense", (d_model, d_model)),
+                                        ("classifier.out_proj", (self.num_labels, d_model))):
+                p[name + ".weight"] = nn.Parameter(torch.randn(n_out, n_in) * 0.02)
+                p[name + ".bias"] = nn.Parameter(torch.zeros(n_out))
+            self._names = list(p)
+        for k, v in p.items():
+            self.register_parameter(k.replace(".", "__"), v)
+        self._qkv = {}  # layer -> ([3D][D] weight, [3D] bias, [D][3D] transposed weight): one GEMM for q, k and v
+        self._saved = None
+
+    # ---- huggingface-compatible state dict -------------------------------------------------
+    def P(self, name):
+        return getattr(self, name.replace(".", "__"))
+
+    def E(self, name):
+        """A parameter of the encoder (under the model's prefix)."""
+        return self.P(self.PREFIX + name)
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        for k in self._names:
+            v = self.P(k)
+            destination[prefix + k] = v if keep_vars else v.detach()
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                              error_msgs):
+        mine = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
+        with torch.no_grad():
+            for k in self._names:
+                if k in mine:
+                    src = torch.as_tensor(mine[k])
+                    if src.shape != self.P(k).shape:
+                        error_msgs.append(f"size mismatch for {prefix + k}: {tuple(src.shape)} vs "
+                                          f"{tuple(self.P(k).shape)}")
+                    else:
+                        self.P(k).copy_(src)
+                else:
+                    missing_keys.append(prefix + k)
+        for k in mine:
+            # checkpoints of the pinned release carry the position-id buffer; newer releases dropped it
+            if k not in self._names and not k.endswith("embeddings.position_ids"):
+                unexpected_keys.append(prefix + k)
+        self._drop_wt()
+
+    def _drop_wt(self):
+        self._qkv.clear()
+
+    def _apply(self, fn, *args, **kwargs):
+        self._qkv.clear()  # device / dtype moves replace the parameters' storage
+        return super()._apply(fn, *args, **kwargs)
+
+    def _fused_qkv(self, i):
+        t = self._qkv.get(i)
+        q = f"encoder.layer.{i}.attention.self."
+        if t is None or t[0].device != self.E(q + "query.weight").device:
+            if torch.cuda.is_current_stream_capturing():
+                raise ops._lib.VsError("RoBERTa's fused q/k/v weights must exist before a graph capture "
+                                       "(run one eager step first)")
+            w = torch.cat([self.E(q + s + ".weight").detach() for s in ("query", "key", "value")], 0).contiguous()
+            b = torch.cat([self.E(q + s + ".bias").detach() for s in ("query", "key", "value")], 0).contiguous()
+            t = (w, b, ops.transpose_f32(w))
+            self._qkv[i] = t
+        return t
+
+    # ---- compute ---------------------------------------------------------------------------
+    def _check(self, tokens, attention_mask):
+        if not tokens.is_cuda:
+            raise ops._lib.VsError("RoBERTa runs on the HIP kernels only (GPU tensor required)")
+        if tokens.dim() != 2:
+            raise ops._lib.VsError("input_ids must be [R, L]")
+        if attention_mask is None:
+            return None
+        if attention_mask.shape != tokens.shape:
+            raise ops._lib.VsError("attention_mask must have the shape of input_ids")
+        return attention_mask.ne(0).to(torch.uint8).contiguous()
+
+    def _dense(self, name, x):
+        return ops.gemm_nt(x, self.E(name + ".weight"), self.E(name + ".bias"))
+
+    def _encode(self, tokens, attention_mask, keep):
+        """-> (last hidden state [R*L, D], saved activations | None)."""
+        km = self._check(tokens, attention_mask)
+        r, l = tokens.shape
+        e, pos_ids = ops.roberta_embed(tokens, self.E("embeddings.word_embeddings.weight"),
+                                       self.E("embeddings.position_embeddings.weight"),
+                                       self.E("embeddings.token_type_embeddings.weight"), self.pad)
+        h, mean0, rstd0 = ops.add_layernorm_fwd(e, None, self.E("embeddings.LayerNorm.weight"),
+                                                self.E("embeddings.LayerNorm.bias"), self.eps)
+        layers = []
+        for i in range(self.n_layer):
+            q = f"encoder.layer.{i}."
+            w, b, _ = self._fused_qkv(i)
+            qkv = ops.gemm_nt(h, w, b)
+            ctx = ops.attn_pad(qkv, km, r, l, self.n_head)
+            ao = self._dense(q + "attention.output.dense", ctx)
+            h1, mean1, rstd1 = ops.add_layernorm_fwd(ao, h, self.E(q + "attention.output.LayerNorm.weight"),
+                                                     self.E(q + "attention.output.LayerNorm.bias"), self.eps)
+            f_pre = self._dense(q + "intermediate.dense", h1)
+            f = ops.gelu_erf_fwd(f_pre)
+            fo = self._dense(q + "output.dense", f)
+            h2, mean2, rstd2 = ops.add_layernorm_fwd(fo, h1, self.E(q + "output.LayerNorm.weight"),
+                                                     self.E(q + "output.LayerNorm.bias"), self.eps)
+            if keep:
+                layers.append((h, qkv, ctx, ao, mean1, rstd1, h1, f_pre, f, fo, mean2, rstd2))
+            h = h2
+        saved = (tokens, pos_ids, km, r, l, e, mean0, rstd0, layers) if keep else None
+        return h, saved
+
+    def _first_token(self, h, r, l):
+        return h.view(r, l, self.d_model)[:, 0].contiguous()
+
+    def _grad(self, name):
+        p = self.E(name) if not name.startswith("classifier.") else self.P(name)
+        if p.grad is None:
+            p.grad = torch.empty_like(p)
+        return p.grad
+
+    def _dense_bwd(self, name, x, dy, need_dx=True):
+        """y = x W^T + b, W [out, in]: dW = dy^T x, db = colsum(dy), dx = dy W."""
+        ops.gemm_nt(ops.transpose_f32(dy), ops.transpose_f32(x), out=self._grad(name + ".weight"))
+        ops.colsum_f32(dy, out=self._grad(name + ".bias"))
+        if not need_dx:
+            return None
+        w = self.E(name + ".weight") if not name.startswith("classifier.") else self.P(name + ".weight")
+        return ops.gemm_nt(dy, ops.transpose_f32(w))
+
+    def _encode_bwd(self, saved, dh):
+        """dh [R*L, D]: gradient of the last hidden state -> every encoder / embedding parameter's .grad."""
+        tokens, pos_ids, km, r, l, e, mean0, rstd0, layers = saved
+        d = self.d_model
+        for i in reversed(range(self.n_layer)):
+            q = f"encoder.layer.{i}."
+            h_in, qkv, ctx, ao, mean1, rstd1, h1, f_pre, f, fo, mean2, rstd2 = layers[i]
+            ds2 = ops.add_layernorm_bwd(dh, fo, h1, self.E(q + "output.LayerNorm.weight"), mean2, rstd2,
+                                        dg_out=self._grad(q + "output.LayerNorm.weight"),
+                                        db_out=self._grad(q + "output.LayerNorm.bias"))[0]
+            df = self._dense_bwd(q + "output.dense", f, ds2)
+            df_pre = ops.gelu_erf_bwd(df, f_pre)
+            dh1 = ops.add_f32(self._dense_bwd(q + "intermediate.dense", h1, df_pre), ds2)
+            ds1 = ops.add_layernorm_bwd(dh1, ao, h_in, self.E(q + "attention.output.LayerNorm.weight"), mean1, rstd1,
+                                        dg_out=self._grad(q + "attention.output.LayerNorm.weight"),
+                                        db_out=self._grad(q + "attention.output.LayerNorm.bias"))[0]
+            dctx = self._dense_bwd(q + "attention.output.dense", ctx, ds1)
+            dqkv = ops.attn_pad_bwd(qkv, km, dctx, r, l, self.n_head)
+            # the fused projection: weight gradients straight into the three separate parameters
+            _, _, wt = self._fused_qkv(i)
+            dqkv_t, h_t = ops.transpose_f32(dqkv), ops.transpose_f32(h_in)
+            db = ops.colsum_f32(dqkv)
+            for s, nm in enumerate(("query", "key", "value")):
+                ops.gemm_nt(dqkv_t[s * d:(s + 1) * d], h_t, out=self._grad(q + "attention.self." + nm + ".weight"))
+                self._grad(q + "attention.self." + nm + ".bias").copy_(db[s * d:(s + 1) * d])
+            dh = ops.add_f32(ops.gemm_nt(dqkv, wt), ds1)
+            layers[i] = None
+        de = ops.add_layernorm_bwd(dh, e, None, self.E("embeddings.LayerNorm.weight"), mean0, rstd0,
+                                   dg_out=self._grad("embeddings.LayerNorm.weight"),
+                                   db_out=self._grad("embeddings.LayerNorm.bias"))[0]
+        dword = self._grad("embeddings.word_embeddings.weight")
+        dpos = self._grad("embeddings.position_embeddings.weight")
+        dword.zero_()
+        dpos.zero_()
+        # both tables have padding_idx = pad: vs_embed_scatter_bwd skips those rows
+        ops.embed_scatter_bwd(tokens, de, dword, 1.0, self.pad)
+        ops.embed_scatter_bwd(pos_ids, de, dpos, 1.0, self.pad)
+        ops.colsum_f32(de, out=self._grad("embeddings.token_type_embeddings.weight").view(-1))
+        self._drop_wt()  # the optimizer is about to change the parameters
+
+    def take_train_state(self):
+        st, self._saved = self._saved, None
+        return st
+
+    def put_train_state(self, st):
+        self._saved = st
+
+
+class RobertaModelHip(_RobertaHip):
+    """`RobertaModel(add_pooling_layer=True)`: `forward(input_ids, attention_mask)` -> object with
+    `last_hidden_state` [R, L, D] and `pooler_output` [R, D]."""
+
+    def __init__(self, *args, add_pooling_layer=True, **kw):
+        super().__init__(*args, add_pooling_layer=add_pooling_layer, num_labels=0, **kw)
+
+    def _outputs(self, tokens, attention_mask, keep):
+        r, l = tokens.shape
+        h, saved = self._encode(tokens, attention_mask, keep)
+        pooled = None
+        x0 = None
+        if self.has_pooler:
+            x0 = self._first_token(h, r, l)
+            pooled = ops.tanh_fwd(self._dense("pooler.dense", x0))
+        if keep:
+            self._saved = (saved, x0, pooled)
+        return h.view(r, l, self.d_model), pooled
+
+    @torch.no_grad()
+    def forward(self, input_ids, attention_mask=None, return_dict=True):
+        h, pooled = self._outputs(input_ids, attention_mask, keep=False)
+        return _Out(last_hidden_state=h, pooler_output=pooled)
+
+    @torch.no_grad()
+    def forward_train(self, input_ids, attention_mask=None):
+        """-> (last_hidden_state, pooler_output), keeping what `backward` needs."""
+        return self._outputs(input_ids, attention_mask, keep=True)
+
+    @torch.no_grad()
+    def backward(self, dhidden, dpooled=None):
+        """Gradients of the two outputs (either may be None) -> .grad of every parameter that took part."""
+        saved, x0, pooled = self._saved
+        self._saved = None
+        r, l = saved[3], saved[4]
+        if dhidden is not None:
+            dh = dhidden.reshape(r * l, self.d_model).contiguous().clone()
+        else:
+            dh = torch.zeros((r * l, self.d_model), dtype=torch.float32, device=saved[0].device)
+        if dpooled is not None and self.has_pooler:
+            dpre = ops.tanh_bwd(dpooled.contiguous(), pooled)
+            dx0 = self._dense_bwd("pooler.dense", x0, dpre)
+            dh.view(r, l, self.d_model)[:, 0] += dx0
+        self._encode_bwd(saved, dh)
+
+
+class RobertaForSequenceClassificationHip(_RobertaHip):
+    """`RobertaForSequenceClassification(num_labels)`: encoder without pooler under `roberta.`, head
+    `classifier.out_proj(tanh(classifier.dense(h[:, 0])))`; `forward` -> object with `logits` [R, num_labels]."""
+
+    PREFIX = "roberta."
+
+    def __init__(self, *args, num_labels=2, **kw):
+        super().__init__(*args, add_pooling_layer=False, num_labels=num_labels, **kw)
+
+    def _outputs(self, tokens, attention_mask, keep):
+        r, l = tokens.shape
+        h, saved = self._encode(tokens, attention_mask, keep)
+        x0 = self._first_token(h, r, l)
+        c1 = ops.tanh_fwd(ops.gemm_nt(x0, self.P("classifier.dense.weight"), self.P("classifier.dense.bias")))
+        logits = ops.gemm_nt(c1, self.P("classifier.out_proj.weight"), self.P("classifier.out_proj.bias"))
+        if keep:
+            self._saved = (saved, x0, c1)
+        return (logits,)
+
+    @torch.no_grad()
+    def forward(self, input_ids, attention_mask=None, return_dict=True):
+        return _Out(logits=self._outputs(input_ids, attention_mask, keep=False)[0])
+
+    @torch.no_grad()
+    def forward_train(self, input_ids, attention_mask=None):
+        return self._outputs(input_ids, attention_mask, keep=True)
+
+    @torch.no_grad()
+    def backward(self, dlogits):
+        saved, x0, c1 = self._saved
+        self._saved = None
+        r, l = saved[3], saved[4]
+        dc1 = self._dense_bwd("classifier.out_proj", c1, dlogits.contiguous())
+        dx0 = self._dense_bwd("classifier.dense", x0, ops.tanh_bwd(dc1, c1))
+        dh = torch.zeros((r * l, self.d_model), dtype=torch.float32, device=dx0.device)
+        dh.view(r, l, self.d_model)[:, 0] = dx0
+        self._encode_bwd(saved, dh)
+
+
+class _Out(dict):
+    """The `return_dict=True` output: keys are attributes too."""
+
+    __getattr__ = dict.get
+
+
+class _RobertaTrainFn(torch.autograd.Function):
+    """One autograd node for the whole encoder (manual HIP backward); the saved activations travel with the node."""
+
+    @staticmethod
+    def forward(ctx, model, tokens, mask, _tick):
+        ctx.model = model
+        ctx.set_materialize_grads(False)  # an output nobody used arrives as None, not as a tensor of zeros
+        outs = model.forward_train(tokens, mask)
+        ctx.saved_state = model.take_train_state()
+        ctx.present = [o is not None for o in outs]
+        return tuple(o for o in outs if o is not None)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        it = iter(grads)
+        full = [next(it) if present else None for present in ctx.present]
+        ctx.model.put_train_state(ctx.saved_state)
+        ctx.model.backward(*[g.contiguous() if g is not None else None for g in full])
+        return None, None, None, None
+
+
+def roberta_apply(model, tokens, mask):
+    """The model's outputs as tensors autograd can differentiate through (training), or the plain forward's."""
+    if model.training and torch.is_grad_enabled():
+        tick = torch.zeros(1, device=tokens.device, requires_grad=True)
+        return _RobertaTrainFn.apply(model, tokens, mask, tick)
+    with torch.no_grad():
+        outs = model._outputs(tokens, mask, keep=False)
+    return tuple(o for o in outs if o is not None)
+
+
+def build(name, cls, state_dict=None, **kw):
+    """`cls(**ROBERTA_DIMS[name])`, loading `state_dict` when one is given (the `from_pretrained` of this package)."""
+    if name not in ROBERTA_DIMS:
+        raise NotImplementedError(f"rob_mdl_name={name}: known dimensions are {sorted(ROBERTA_DIMS)}")
+    m = cls(**ROBERTA_DIMS[name], **kw)
+    if state_dict is not None:
+        m.load_state_dict(state_dict)
+    return m

@@ -6,7 +6,13 @@ outside it raise NotImplementedError exactly like an unknown name does upstream
 """
 from .mdl_sf_base import (SFBase, SFBase_TxEnc, LossB, LossLambda, SFPreFeats_TxDec, SFPreFeats_TxEncDec,
                           Simple_GPT2_New, Simple_TxDec)
-from .evl_vsitu import EvalB, EvalB_Gen
+from .mdl_evrel import (Simple_EvRel_Roberta, SFPret_SimpleEvRel, SFPret_OnlyVb_SimpleEvRel,
+                        SFPret_OnlyVid_SimpleEvRel, Simple_TxEncEvRel)
+from .evl_vsitu import EvalB, EvalB_Acc, EvalB_Gen
+
+# `vidsitu_code/mdl_selector.py:47-69`
+_EVREL = {"rob_evrel": Simple_EvRel_Roberta, "txe_evrel": Simple_TxEncEvRel, "sfpret_evrel": SFPret_SimpleEvRel,
+          "sfpret_vbonly_evrel": SFPret_OnlyVb_SimpleEvRel, "sfpret_onlyvid_evrel": SFPret_OnlyVid_SimpleEvRel}
 
 
 def get_mdl_loss_eval(cfg):
@@ -26,6 +32,10 @@ def get_mdl_loss_eval(cfg):
             return {"mdl": SFPreFeats_TxDec, "loss": LossLambda, "evl": EvalB_Gen}
         if cfg.mdl.mdl_name == "sfpret_txe_txd_vbarg":
             return {"mdl": SFPreFeats_TxEncDec, "loss": LossLambda, "evl": EvalB_Gen}
+        raise NotImplementedError
+    elif cfg.task_type == "evrel":
+        if cfg.mdl.mdl_name in _EVREL:
+            return {"mdl": _EVREL[cfg.mdl.mdl_name], "loss": LossLambda, "evl": EvalB_Acc}
         raise NotImplementedError
     else:
         raise NotImplementedError

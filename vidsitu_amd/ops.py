@@ -1550,3 +1550,79 @@ def colsum_bf16(x, out=None):
     ld = act_ld4(x) if c == 4 else act_ld(x)  # (the stems' packed C = 4 input)
     _lib.call("vs_colsum_bf16", _ptr(x), _ptr(out), n * t * h * w, c, ld, _stream())
     return out
+
+
+# ---- RoBERTa encoder (csrc/roberta_ops.hip) ------------------------------------------------------
+def _key_mask_u8(key_mask, r, l):
+    if key_mask is None:
+        return None
+    if key_mask.dtype != torch.uint8 or tuple(key_mask.shape) != (r, l):
+        raise _lib.VsError(f"key_mask must be uint8 [{r}, {l}]")
+    return key_mask.contiguous()
+
+
+def attn_pad(qkv, key_mask, r, l, n_head):
+    """Bidirectional padding-masked self-attention: qkv f32 [R*L, 3D]; key_mask uint8 [R, L] or None -> f32 [R*L, D]."""
+    qkv = _f32c(qkv)
+    d = qkv.shape[1] // 3
+    if qkv.shape[0] != r * l or qkv.shape[1] != 3 * d or d % n_head:
+        raise _lib.VsError(f"attn_pad: qkv {tuple(qkv.shape)} is not [{r}*{l}, 3*D] with D % {n_head} == 0")
+    out = torch.empty((r * l, d), dtype=torch.float32, device=qkv.device)
+    _lib.call("vs_attn_pad_fwd", _ptr(qkv), _ptr(_key_mask_u8(key_mask, r, l)), _ptr(out), r, l, n_head,
+              d // n_head, _stream())
+    return out
+
+
+def attn_pad_bwd(qkv, key_mask, dout, r, l, n_head):
+    qkv = _f32c(qkv)
+    d = qkv.shape[1] // 3
+    if qkv.shape[0] != r * l or dout.numel() != r * l * d or d % n_head:
+        raise _lib.VsError("attn_pad_bwd: shapes of qkv / dout do not match R, L")
+    dqkv = torch.empty_like(qkv)
+    need = _lib.load().vs_attn_pad_bwd_scratch_bytes(r, l, n_head)
+    ws = _workspace(need, qkv.device)
+    _lib.call("vs_attn_pad_bwd", _ptr(qkv), _ptr(_key_mask_u8(key_mask, r, l)), _ptr(_f32c(dout)), _ptr(dqkv),
+              _ptr(ws), C.c_size_t(ws.numel()), r, l, n_head, d // n_head, _stream())
+    return dqkv
+
+
+def roberta_embed(tokens, word, pos, type0, pad):
+    """tokens i64 [R, L] -> (f32 [R*L, D] = word[tok] + pos[pos_id] + type0, pos_id i64 [R, L])."""
+    tokens = tokens.contiguous()
+    if tokens.dtype != torch.int64:
+        raise _lib.VsError("roberta_embed: int64 token ids expected")
+    r, l = tokens.shape
+    d = word.shape[1]
+    out = torch.empty((r * l, d), dtype=torch.float32, device=word.device)
+    pos_ids = torch.empty((r, l), dtype=torch.int64, device=word.device)
+    _lib.call("vs_roberta_embed", _ptr(tokens), _ptr(_f32c(word)), _ptr(_f32c(pos)), _ptr(_f32c(type0)), _ptr(out),
+              _ptr(pos_ids), r, l, d, int(pad), pos.shape[0], _stream())
+    return out, pos_ids
+
+
+def gelu_erf_fwd(x):
+    x = _f32c(x)
+    y = torch.empty_like(x)
+    _lib.call("vs_gelu_erf_fwd", _ptr(x), _ptr(y), x.numel(), _stream())
+    return y
+
+
+def gelu_erf_bwd(dy, x_pre):
+    dy, x_pre = _f32c(dy), _f32c(x_pre)
+    dx = torch.empty_like(dy)
+    _lib.call("vs_gelu_erf_bwd", _ptr(dy), _ptr(x_pre), _ptr(dx), dy.numel(), _stream())
+    return dx
+
+
+def tanh_fwd(x):
+    x = _f32c(x)
+    y = torch.empty_like(x)
+    _lib.call("vs_tanh_fwd", _ptr(x), _ptr(y), x.numel(), _stream())
+    return y
+
+
+def tanh_bwd(dy, y):
+    dy, y = _f32c(dy), _f32c(y)
+    dx = torch.empty_like(dy)
+    _lib.call("vs_tanh_bwd", _ptr(dy), _ptr(y), _ptr(dx), dy.numel(), _stream())
+    return dx

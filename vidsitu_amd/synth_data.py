@@ -60,15 +60,35 @@ class SynthGPT2Tok:
         return " ".join(f"t{int(i)}" for i in ids if int(i) not in special)
 
 
+class SynthRobTok:
+    """Stand-in for `comm.rob_hf_tok` (`dat_loader.py:84-86`: a RobertaTokenizerFast): the special-token ids of the
+    roberta vocabulary (`<s>` 0, `<pad>` 1, `</s>` 2, `<unk>` 3) and `len()`."""
+
+    bos_token_id, pad_token_id, eos_token_id, unk_token_id = 0, 1, 2, 3
+
+    def __init__(self, vocab_size):
+        self.vocab_size = vocab_size
+
+    def __len__(self):
+        return self.vocab_size
+
+
+EVREL_DCT = {"Null": 0, "Causes": 1, "Reaction To": 2, "Enables": 3, "NoRel": 4}  # dat_loader.py:124-130
+
+
 def make_comm(cfg):
     sf = cfg.sf_mdl
     arch = sf.MODEL.ARCH
     path_type = "multi" if arch in sf.MODEL.MULTI_PATHWAY_ARCH else "single"
     nv = cfg.synth.num_verbs if "synth" in cfg else 1564
     ntok = cfg.synth.gpt2_vocab if ("synth" in cfg and "gpt2_vocab" in cfg.synth) else 50259
+    from .hf_roberta import ROBERTA_DIMS
+
+    rob = ROBERTA_DIMS.get(cfg.mdl.get("rob_mdl_name", "roberta-base"), ROBERTA_DIMS["roberta-base"])
     return SimpleNamespace(path_type=path_type, vb_id_vocab=[f"verb_{i}" for i in range(nv)],
                            num_frms=sf.DATA.NUM_FRAMES, sampling_rate=sf.DATA.SAMPLING_RATE,
-                           gpt2_hf_tok=SynthGPT2Tok(ntok))
+                           gpt2_hf_tok=SynthGPT2Tok(ntok), rob_hf_tok=SynthRobTok(rob["vocab_size"]),
+                           evrel_dct=dict(EVREL_DCT), evrel_dct_opp={v: k for k, v in EVREL_DCT.items()})
 
 
 def synth_u8_batch(cfg, comm, bs, n_ev=5, seed=1234, device="cpu", crop=None):
@@ -155,6 +175,40 @@ def synth_srl_batch(comm, bs, n_ev=5, n_ann=1, seq_len=60, feat_dim=2304, seed=1
         "frm_feats": torch.randn(bs, n_ev, feat_dim, generator=g).to(device),
         "vseg_idx": torch.arange(bs, dtype=torch.long, device=device),
     }
+
+
+def _rob_sequences(tok, g, lead, seq_len, min_len):
+    """i64 [*lead, seq_len] roberta token sequences `<s> ... </s>` right-padded with `<pad>`, and their {0,1} masks."""
+    seq = torch.full((*lead, seq_len), tok.pad_token_id, dtype=torch.long)
+    mask = torch.zeros((*lead, seq_len), dtype=torch.long)
+    flat_s, flat_m = seq.view(-1, seq_len), mask.view(-1, seq_len)
+    for i in range(flat_s.shape[0]):
+        n = int(torch.randint(min_len, seq_len + 1, (1,), generator=g))  # whole length, <s> and </s> included
+        flat_s[i, 0] = tok.bos_token_id
+        if n > 2:
+            flat_s[i, 1:n - 1] = torch.randint(4, len(tok), (n - 2,), generator=g)
+        flat_s[i, n - 1] = tok.eos_token_id
+        flat_m[i, :n] = 1
+    return seq, mask
+
+
+def synth_evrel_batch(comm, bs, n_ann=1, feat_dim=2304, seed=1234, device="cpu"):
+    """Batch of the evrel contract (`dat_loader.py:342-450`, collated): the paired SRL text `evrel_seq_out`
+    i64 [B,4,n_ann,120], per-event text `evrel_seq_out_ones` [B,5,n_ann,60] and verb-only text
+    `evrel_vbonly_out_ones` [B,5,n_ann,5], each with its `_lens` {0,1} mask; `evrel_labs` i64 [B,4,n_ann] in 0..4;
+    `frm_feats` f32 [B,5,feat_dim]; `vseg_idx`.  Sequences start with `<s>` (0), end with `</s>` (2) and are
+    right-padded with `<pad>` (1)."""
+    tok = comm.rob_hf_tok
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    out = {}
+    for key, n_ev, seq_len, min_len in (("evrel_seq_out", 4, 120, 8), ("evrel_seq_out_ones", 5, 60, 4),
+                                        ("evrel_vbonly_out_ones", 5, 5, 3)):
+        seq, mask = _rob_sequences(tok, g, (bs, n_ev, n_ann), seq_len, min_len)
+        out[key], out[key + "_lens"] = seq.to(device), mask.to(device)
+    out["evrel_labs"] = torch.randint(0, len(comm.evrel_dct), (bs, 4, n_ann), generator=g).to(device)
+    out["frm_feats"] = torch.randn(bs, 5, feat_dim, generator=g).to(device)
+    out["vseg_idx"] = torch.arange(bs, dtype=torch.long, device=device)
+    return out
 
 
 def synth_batch(cfg, comm, bs, n_ev=5, seed=1234, device="cpu", dtype=torch.float32,

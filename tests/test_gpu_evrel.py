@@ -120,6 +120,55 @@ def test_all_zero_mask_row_and_missing_mask(dev):
         assert max(e) < OUT_TOL
 
 
+def _close(a, b):
+    # the embedding backward accumulates rows with atomics: equal up to fp32 summation order
+    return bool(((a - b).abs().max() <= 1e-5 * a.abs().max().clamp_min(1e-12)).item())
+
+
+@pytest.mark.parametrize("both", [True, False], ids=["both_outputs", "pooler_only"])
+def test_two_forwards_keep_their_own_state(both, dev):
+    """Two forwards on different inputs through `roberta_apply`, then the backwards in the opposite order: every
+    parameter gradient equals that of each forward-backward pair run alone.  3 x 9 tokens, one row's tail masked;
+    with a loss on `pooler_output` alone the hidden state's gradient reaches the node as None."""
+    from vidsitu_amd import hf_roberta
+
+    torch.manual_seed(5)
+    m = hf_roberta.build("roberta-synth-tiny", hf_roberta.RobertaModelHip).to(dev).train()
+    pad, d = m.pad, m.d_model
+    g = torch.Generator().manual_seed(6)
+    toks = [torch.randint(2, 101, (3, 9), generator=g) for _ in range(2)]
+    toks[0][2, 5:] = pad
+    toks[1][0, 7:] = pad
+    toks = [t.to(dev) for t in toks]
+    masks = [t.ne(pad) for t in toks]
+    wh = [torch.randn(3, 9, d, generator=g).to(dev) for _ in range(2)]
+    wp = [torch.randn(3, d, generator=g).to(dev) for _ in range(2)]
+    for p in m.parameters():
+        p.grad = torch.zeros_like(p)
+
+    def run(i, scale):
+        hidden, pooled = hf_roberta.roberta_apply(m, toks[i], masks[i])
+        loss = (pooled * wp[i]).sum()
+        if both:
+            loss = loss + (hidden * wh[i]).sum()
+        return loss * scale
+
+    def grads(loss):
+        for p in m.parameters():
+            p.grad.zero_()
+        loss.backward()
+        return [p.grad.clone() for p in m.parameters()]
+
+    want = [grads(run(i, 1.0 + i)) for i in range(2)]
+    assert all(float(w.abs().max()) > 0 for w in want[0])
+    la, lb = run(0, 1.0), run(1, 2.0)
+    got_b = grads(lb)
+    got_a = grads(la)
+    for want_i, got_i in ((want[0], got_a), (want[1], got_b)):
+        for n, w, gt in zip(m._names, want_i, got_i):
+            assert _close(w, gt), n
+
+
 # ---- the five models ------------------------------------------------------------------------------------------------
 def _cfg(row):
     from vidsitu_amd.extended_config import get_cfg

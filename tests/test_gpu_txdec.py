@@ -368,3 +368,53 @@ def test_old_encoder_plus_txdec_plugin_surface_trains(enc_type, dev):
         opt.step()
         losses.append(float(loss.detach()))
     assert all(np.isfinite(losses)) and losses[-1] < losses[0] - 0.2, losses
+
+
+def _close(a, b):
+    # the embedding backward accumulates rows with atomics: equal up to fp32 summation order
+    return bool(((a - b).abs().max() <= 1e-5 * a.abs().max().clamp_min(1e-12)).item())
+
+
+def test_two_forwards_keep_their_own_state(dev):
+    """Two forwards on different inputs, then the backwards in the opposite order: every parameter gradient and
+    the encoder output's gradient equal those of each forward-backward pair run alone (the saved activations
+    travel with the autograd node).  3 x 7 tokens with a padded tail, one encoder position per row."""
+    from vidsitu_amd.fseq_txdec import TransformerDecoderHip
+    from vidsitu_amd.flat_module import FlatTrainFn
+    from vidsitu_amd.hf_gpt2_fseq import lm_loss
+
+    voc, d, pad = 50, 32, 49
+    torch.manual_seed(7)
+    m = TransformerDecoderHip(vocab=voc, d_model=d, ffn=48, n_head=4, n_layer=2, out_dim=16, pad=pad,
+                              dropout=0.0).to(dev).train()
+    g = torch.Generator().manual_seed(8)
+    toks = [torch.randint(0, pad, (3, 7), generator=g) for _ in range(2)]
+    toks[0][1, 4:] = pad
+    toks[1][2, 5:] = pad
+    toks = [t.to(dev) for t in toks]
+    encs = [torch.randn(1, 3, d, generator=g).to(dev).requires_grad_(True) for _ in range(2)]
+    for p in m.parameters():
+        p.grad = torch.zeros_like(p)
+
+    def run(i, scale):
+        tick = torch.zeros(1, device=dev, requires_grad=True)
+        logits = FlatTrainFn.apply(m, toks[i], m.enc_rows(encs[i], 3), tick)
+        return lm_loss(logits, toks[i], pad) * scale
+
+    def grads(loss, i):
+        for p in m.parameters():
+            p.grad.zero_()
+        encs[i].grad = None
+        loss.backward()
+        return [p.grad.clone() for p in m.parameters()] + [encs[i].grad.clone()]
+
+    want = [grads(run(i, 1.0 + i), i) for i in range(2)]
+    assert all(float(w[-1].abs().max()) > 0 for w in want)
+    la, lb = run(0, 1.0), run(1, 2.0)
+    got_b = grads(lb, 1)
+    got_a = grads(la, 0)
+    names = m._names + ["encoder_out"]
+    for want_i, got_i in ((want[0], got_a), (want[1], got_b)):
+        assert tuple(got_i[-1].shape) == (1, 3, d)
+        for n, w, gt in zip(names, want_i, got_i):
+            assert _close(w, gt), n

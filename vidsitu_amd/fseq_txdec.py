@@ -10,8 +10,9 @@ load (`layers.N.self_attn.q_proj.weight`, ...).
   `mdl_sf_base.py:806-832`: `[1, B*n_ev, 1024]`), so the softmax over encoder positions is exactly 1 and
   encoder attention is `out_proj(v_proj(enc))` broadcast over the target positions -- a per-row constant
   (its q / k projections get exactly zero gradient, as autograd gives them).  Longer encoder outputs raise.
-* Training: one autograd node -- forward keeps the activations, a hand-written backward writes every
-  parameter gradient (overwrite semantics) and returns the gradient of the encoder output.  Dropout
+* Training: one autograd node (`flat_module.FlatTrainFn`; `TransformerDecoderHip` is a `FlatParamModule`, which
+  owns registration, state dict and the cached copies) -- forward keeps the activations, a hand-written backward
+  writes every parameter gradient (overwrite semantics) and returns the gradient of the encoder output.  Dropout
   (`dropout` after the embedding and after each sub-layer; attention / activation dropout are 0 in the
   reference's YAML) through mask operands of the fused add + layernorm kernel.
 * Generation: a KV cache per layer read through the beam ancestry table (`vs_attn_decode`), the encoder
@@ -24,7 +25,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .hf_gpt2_fseq import KVCacheState
+from .flat_module import FlatParamModule, FlatTrainFn
 from .transformer_code import AddLayerNormFn, AttnSmallFn, hip_linear
 
 
@@ -34,7 +35,10 @@ def _xavier(out_f, in_f, gain=1.0):
     return t
 
 
-class TransformerDecoderHip(nn.Module):
+class TransformerDecoderHip(FlatParamModule):
+    _CACHES = ("_cat",)  # layer -> concatenated q | k | v projection
+    _CAPTURE_MSG = "decoder weight copies must exist before a graph capture (run one eager step)"
+
     def __init__(self, vocab, d_model, ffn, n_head, n_layer, out_dim, pad, dropout=0.1, max_positions=1024):
         super().__init__()
         self.vocab, self.d_model, self.ffn, self.n_head, self.n_layer = vocab, d_model, ffn, n_head, n_layer
@@ -58,78 +62,29 @@ class TransformerDecoderHip(nn.Module):
             p[q + "final_layer_norm.bias"] = torch.zeros(d_model)
         p["project_out_dim.weight"] = _xavier(out_dim, d_model)
         p["output_projection.weight"] = torch.randn(vocab, out_dim) * out_dim ** -0.5
-        self._names = list(p)
-        for k, v in p.items():
-            self.register_parameter(k.replace(".", "__"), nn.Parameter(v))
-        self._cat, self._tab = {}, {}
-        self._wt_epoch = 0  # bumped when cached weight copies are dropped (captured decode graphs go stale)
-        self._saved = None
+        self._register_flat(p)
+        self._tab = {}  # device -> position table (derived from no parameter: survives `_drop_copies`)
 
     # ---- fairseq-compatible state dict -------------------------------------------------------------
-    def P(self, name):
-        return getattr(self, name.replace(".", "__"))
-
-    def _save_to_state_dict(self, destination, prefix, keep_vars):
-        for k in self._names:
-            v = self.P(k)
-            destination[prefix + k] = v if keep_vars else v.detach()
+    def _extra_state(self, prefix, keep_vars):
         dev = self.P("embed_tokens.weight").device
-        destination[prefix + "embed_positions._float_tensor"] = torch.zeros(1, device=dev)
-        destination[prefix + "version"] = torch.tensor([3.0], device=dev)
+        return {prefix + "embed_positions._float_tensor": torch.zeros(1, device=dev),
+                prefix + "version": torch.tensor([3.0], device=dev)}
 
-    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
-                              error_msgs):
-        mine = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
-        with torch.no_grad():
-            for k in self._names:
-                if k not in mine:
-                    missing_keys.append(prefix + k)
-                elif tuple(mine[k].shape) != tuple(self.P(k).shape):
-                    error_msgs.append(f"size mismatch for {prefix + k}: {tuple(mine[k].shape)} vs "
-                                      f"{tuple(self.P(k).shape)}")
-                else:
-                    self.P(k).copy_(torch.as_tensor(mine[k]))
-        for k in mine:
-            if k not in self._names and k not in ("embed_positions._float_tensor", "version"):
-                unexpected_keys.append(prefix + k)
-        self._drop()
-
-    def _drop(self):
-        self._cat.clear()
-        self._wt_epoch += 1
-
-    def _guard_capture(self):
-        if torch.cuda.is_current_stream_capturing():
-            raise ops._lib.VsError("decoder weight copies must exist before a graph capture (run one eager step)")
+    def _tolerated_on_load(self, key):
+        return key in ("embed_positions._float_tensor", "version")
 
     def _qkv(self, i):
         """Concatenated self-attention projection [3d, d] / [3d] of layer i (q | k | v)."""
-        t = self._cat.get(i)
-        w0 = self.P(f"layers.{i}.self_attn.q_proj.weight")
-        if t is None or t[0].device != w0.device:
-            self._guard_capture()
-            q = f"layers.{i}.self_attn."
-            t = (torch.cat([self.P(q + f"{n}_proj.weight").detach() for n in "qkv"]).contiguous(),
-                 torch.cat([self.P(q + f"{n}_proj.bias").detach() for n in "qkv"]).contiguous())
-            self._cat[i] = t
-        return t
+        q = f"layers.{i}.self_attn."
+        return self._copy(self._cat, i, self.P(q + "q_proj.weight"), lambda: (
+            torch.cat([self.P(q + f"{n}_proj.weight").detach() for n in "qkv"]).contiguous(),
+            torch.cat([self.P(q + f"{n}_proj.bias").detach() for n in "qkv"]).contiguous()))
 
     def _pos_table(self, device):
-        """Row 0 = zeros (padding); row 1 + t = the sinusoid of position padding_idx + 1 + t, computed on
-        the CPU in fp32 in the order of fairseq's `SinusoidalPositionalEmbedding.get_embedding`."""
-        t = self._tab.get(str(device))
-        if t is None:
-            self._guard_capture()
-            d, half = self.d_model, self.d_model // 2
-            freq = torch.exp(torch.arange(half, dtype=torch.float) * -(math.log(10000) / (half - 1)))
-            pos = torch.arange(self.pad + 1, self.pad + 1 + self.max_positions, dtype=torch.float)
-            ang = pos.unsqueeze(1) * freq.unsqueeze(0)
-            tab = torch.cat([torch.sin(ang), torch.cos(ang)], dim=1)
-            if d % 2 == 1:
-                tab = torch.cat([tab, torch.zeros(tab.shape[0], 1)], dim=1)
-            t = torch.cat([torch.zeros(1, d), tab]).contiguous().to(device)
-            self._tab[str(device)] = t
-        return t
+        """Row 0 = zeros (padding); row 1 + t = the sinusoid of position padding_idx + 1 + t."""
+        return self._copy(self._tab, str(device), self.P("embed_tokens.weight"),
+                          lambda: sinusoid_table(self.pad, self.max_positions, self.d_model, device))
 
     def _embed(self, tokens, pos0=None):
         """tokens i64 [R, L] -> f32 [R*L, d]; pos0: every token sits at target position pos0 (one
@@ -216,19 +171,6 @@ class TransformerDecoderHip(nn.Module):
         return self._forward_seq(tokens, enc2d, train=True)
 
     # ---- backward ------------------------------------------------------------------------------------
-    def _grad(self, name):
-        p = self.P(name)
-        if p.grad is None:
-            p.grad = torch.empty_like(p)
-        return p.grad
-
-    def _lin_bwd(self, name, x, dy, bias=True, need_dx=True):
-        """y = x @ W^T + b with fairseq's W [out, in]: dW = dy^T x, db = colsum(dy), dx = dy @ W."""
-        ops.gemm_nt(ops.transpose_f32(dy), ops.transpose_f32(x), out=self._grad(name + ".weight"))
-        if bias:
-            ops.colsum_f32(dy, out=self._grad(name + ".bias"))
-        return ops.gemm_nt(dy, ops.transpose_f32(self.P(name + ".weight"))) if need_dx else None
-
     @torch.no_grad()
     def backward(self, dlogits):
         """dlogits [R*L, V] -> every parameter's .grad (overwritten); returns d(enc2d) [R, d] or None."""
@@ -236,8 +178,8 @@ class TransformerDecoderHip(nn.Module):
         self._saved = None
         d = self.d_model
         dlogits = dlogits.reshape(r * l, -1)
-        dpo = self._lin_bwd("output_projection", po, dlogits, bias=False)
-        dx = self._lin_bwd("project_out_dim", x_last, dpo, bias=False)
+        dpo = self._linear_bwd("output_projection", po, dlogits, bias=False)
+        dx = self._linear_bwd("project_out_dim", x_last, dpo, bias=False)
         denc = None
         for i in reversed(range(self.n_layer)):
             q = f"layers.{i}."
@@ -245,16 +187,16 @@ class TransformerDecoderHip(nn.Module):
             dx2_a, df2, _, _ = ops.add_layernorm_bwd(dx, x2, f2, self.P(q + "final_layer_norm.weight"), mu3, rs3,
                                                      rmask=m3, dg_out=self._grad(q + "final_layer_norm.weight"),
                                                      db_out=self._grad(q + "final_layer_norm.bias"))
-            df1 = ops.relu_bwd(self._lin_bwd(q + "fc2", f1, df2), f1)
-            dx2 = ops.add_f32(dx2_a, self._lin_bwd(q + "fc1", x2, df1))
+            df1 = ops.relu_bwd(self._linear_bwd(q + "fc2", f1, df2), f1)
+            dx2 = ops.add_f32(dx2_a, self._linear_bwd(q + "fc1", x2, df1))
             if enc2d is not None:
                 dx1, dca, _, _ = ops.add_layernorm_bwd(dx2, x1, ca, self.P(q + "encoder_attn_layer_norm.weight"),
                                                        mu2, rs2, rmask=m2,
                                                        dg_out=self._grad(q + "encoder_attn_layer_norm.weight"),
                                                        db_out=self._grad(q + "encoder_attn_layer_norm.bias"))
                 dco = dca.view(r, l, d).sum(dim=1)
-                dcv = self._lin_bwd(q + "encoder_attn.out_proj", cv, dco)
-                de = self._lin_bwd(q + "encoder_attn.v_proj", enc2d, dcv)
+                dcv = self._linear_bwd(q + "encoder_attn.out_proj", cv, dco)
+                de = self._linear_bwd(q + "encoder_attn.v_proj", enc2d, dcv)
                 denc = de if denc is None else ops.add_f32(denc, de)
                 for pr in ("q_proj", "k_proj"):  # softmax over one key: no gradient reaches q / k
                     self._grad(q + f"encoder_attn.{pr}.weight").zero_()
@@ -267,7 +209,7 @@ class TransformerDecoderHip(nn.Module):
             dx_a, dsa, _, _ = ops.add_layernorm_bwd(dx1, x, sa, self.P(q + "self_attn_layer_norm.weight"), mu1, rs1,
                                                     rmask=m1, dg_out=self._grad(q + "self_attn_layer_norm.weight"),
                                                     db_out=self._grad(q + "self_attn_layer_norm.bias"))
-            do = self._lin_bwd(q + "self_attn.out_proj", o, dsa)
+            do = self._linear_bwd(q + "self_attn.out_proj", o, dsa)
             dqkv = ops.attn_causal_bwd(qkv, km, do, r, l, self.n_head)
             wqkv, _ = self._qkv(i)
             dw = ops.gemm_nt(ops.transpose_f32(dqkv), ops.transpose_f32(x))  # [3d, d]
@@ -281,7 +223,7 @@ class TransformerDecoderHip(nn.Module):
         demb = self._grad("embed_tokens.weight")
         demb.zero_()
         ops.embed_scatter_bwd(tokens, dx, demb, math.sqrt(d), self.pad)
-        self._drop()  # the optimizer is about to change the parameters
+        self._drop_copies()  # the optimizer is about to change the parameters
         return denc
 
     # ---- incremental decoding --------------------------------------------------------------------------
@@ -335,38 +277,12 @@ class TransformerDecoderHip(nn.Module):
         table instead): row r becomes old row new_order[r]."""
         if state.k is None:
             return
-        if state.anc is not None:
-            raise ops._lib.VsError("this cache is reordered through its ancestry table (vs_beam_step)")
-        rows = new_order.numel()
-        if state.k2 is None:
-            state.k2, state.v2 = torch.empty_like(state.k), torch.empty_like(state.v)
-        for li in range(self.n_layer):
-            ops.kv_gather(state.k[li], state.k2[li], new_order, state.len)
-            ops.kv_gather(state.v[li], state.v2[li], new_order, state.len)
-        state.k, state.k2 = state.k2, state.k
-        state.v, state.v2 = state.v2, state.v
+        state.reorder(new_order, self.n_layer)
         if getattr(state, "cross", None) is not None:
             state.cross = state.cross.index_select(1, new_order)
-        state.rows = rows
 
 
-class _TxDecTrainFn(torch.autograd.Function):
-    """logits = decoder(tokens, enc) as one autograd node (`enc` may be None)."""
-
-    @staticmethod
-    def forward(ctx, model, tokens, enc2d, _tick):
-        ctx.model = model
-        ctx.has_enc = enc2d is not None
-        out = model.forward_train(tokens, None if enc2d is None else enc2d.detach())
-        # the saved activations of THIS forward travel with the node (several forwards may precede a backward)
-        ctx.saved_state, model._saved = model._saved, None
-        return out
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        ctx.model._saved = ctx.saved_state
-        denc = ctx.model.backward(dlogits.contiguous())
-        return None, None, (denc if ctx.has_enc else None), None
+_TxDecTrainFn = FlatTrainFn  # the name tests/test_gpu_txdec.py imports
 
 
 class TxDecoderReal(nn.Module):
@@ -402,7 +318,7 @@ class TxDecoderReal(nn.Module):
         enc2d = m.enc_rows(encoder_out, prev_output_tokens.size(0))
         if self.training and torch.is_grad_enabled():
             tick = torch.zeros(1, device=prev_output_tokens.device, requires_grad=True)
-            return (_TxDecTrainFn.apply(m, prev_output_tokens, enc2d, tick),)
+            return (FlatTrainFn.apply(m, prev_output_tokens, enc2d, tick),)
         return (m.forward_logits(prev_output_tokens, enc2d),)
 
     def reorder_incremental_state(self, incremental_state, new_order):

@@ -14,6 +14,9 @@ Incremental decoding: the reference passes empty (falsy) `incremental_state` dic
 re-encodes the whole prefix every step.  The same call with
 `incremental_state=None` does that here; given a `KVCacheState` the decoder appends one position to
 a KV cache instead -- identical arithmetic, one token of work per step.
+
+`GPT2LMHeadModelHip` is a `flat_module.FlatParamModule`: registration, state dict, the cached weight copies and the
+autograd node (`FlatTrainFn`) live there; this file keeps the names / shapes, the arithmetic and `KVCacheState`.
 """
 import math
 
@@ -21,6 +24,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .flat_module import FlatParamModule, FlatTrainFn
 
 GPT2_DIMS = {
     # name: (n_layer, d_model, n_head, n_positions, vocab)
@@ -44,8 +48,27 @@ class KVCacheState:
     def __bool__(self):
         return True
 
+    def reorder(self, new_order, n_layer):
+        """fairseq reorder_incremental_state as a physical gather: row r of the cache becomes old row new_order[r]."""
+        if self.k is None:
+            return
+        if self.anc is not None:
+            raise ops._lib.VsError("this cache is reordered through its ancestry table (vs_beam_step)")
+        if self.k2 is None:
+            self.k2, self.v2 = torch.empty_like(self.k), torch.empty_like(self.v)
+        for li in range(n_layer):
+            ops.kv_gather(self.k[li], self.k2[li], new_order, self.len)
+            ops.kv_gather(self.v[li], self.v2[li], new_order, self.len)
+        self.k, self.k2 = self.k2, self.k
+        self.v, self.v2 = self.v2, self.v
+        self.rows = new_order.numel()
 
-class GPT2LMHeadModelHip(nn.Module):
+
+class GPT2LMHeadModelHip(FlatParamModule):
+    _CACHES = ("_wt",   # K-contiguous ([out][in]) copies of the Conv1D weights for the kernels
+               "_wpk")  # fragment-major copies for the decode-step GEMMs (ops.gemm_nt_packed)
+    _CAPTURE_MSG = "GPT-2 weight copies must exist before a graph capture (run one eager step first)"
+
     def __init__(self, n_layer, d_model, n_head, n_positions, vocab_size):
         super().__init__()
         self.n_layer, self.d_model, self.n_head, self.n_positions = n_layer, d_model, n_head, n_positions
@@ -75,45 +98,16 @@ class GPT2LMHeadModelHip(nn.Module):
             add(q + "mlp.c_proj.bias", d_model, std=0)
         add("transformer.ln_f.weight", d_model, ones=True)
         add("transformer.ln_f.bias", d_model, std=0)
-        # flat registration under the huggingface names ('.' is not allowed in parameter names)
-        self._names = list(p)
-        for k, v in p.items():
-            self.register_parameter(k.replace(".", "__"), v)
-        self._wt = {}  # K-contiguous ([out][in]) copies of the Conv1D weights for the kernels
-        self._wt_epoch = 0  # bumped whenever the copies are dropped (captured decode graphs go stale)
-        self._wpk = {}  # fragment-major copies for the decode-step GEMMs (ops.gemm_nt_packed)
+        self._register_flat(p)
 
     # ---- huggingface-compatible state dict -------------------------------------------------
-    def P(self, name):
-        return getattr(self, name.replace(".", "__"))
-
-    def _save_to_state_dict(self, destination, prefix, keep_vars):
-        for k in self._names:
-            v = self.P(k)
-            destination[prefix + k] = v if keep_vars else v.detach()
+    def _extra_state(self, prefix, keep_vars):
         w = self.P("transformer.wte.weight")
-        destination[prefix + "lm_head.weight"] = w if keep_vars else w.detach()  # tied
+        return {prefix + "lm_head.weight": w if keep_vars else w.detach()}  # tied
 
-    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys,
-                              unexpected_keys, error_msgs):
-        mine = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
-        with torch.no_grad():
-            for k in self._names:
-                if k in mine:
-                    src = torch.as_tensor(mine[k])
-                    if src.shape != self.P(k).shape:
-                        error_msgs.append(f"size mismatch for {prefix + k}: {tuple(src.shape)} vs "
-                                          f"{tuple(self.P(k).shape)}")
-                    else:
-                        self.P(k).copy_(src)
-                else:
-                    missing_keys.append(prefix + k)
-        for k in mine:
-            # huggingface checkpoints also carry the causal-mask buffers of every block
-            if k not in self._names and k != "lm_head.weight" and not k.endswith(".attn.bias") \
-                    and not k.endswith(".attn.masked_bias"):
-                unexpected_keys.append(prefix + k)
-        self._drop_wt()
+    def _tolerated_on_load(self, key):
+        # huggingface checkpoints also carry the causal-mask buffers of every block
+        return key == "lm_head.weight" or key.endswith((".attn.bias", ".attn.masked_bias"))
 
     def resize_token_embeddings(self, new_size):
         """transformers PreTrainedModel.resize_token_embeddings: keep the first rows, initialise
@@ -126,35 +120,18 @@ class GPT2LMHeadModelHip(nn.Module):
         new[:n] = old.detach()[:n]
         setattr(self, "transformer__wte__weight", nn.Parameter(new))
         self.config.vocab_size = new_size
-
-    def _drop_wt(self):
-        self._wt.clear()
-        self._wpk.clear()
-        self._wt_epoch += 1
+        self._drop_copies()  # `_wpk` may hold a packed copy of the old table
 
     def _wp(self, name, transposed=True):
         """Fragment-major copy of a weight ([out][in] orientation) for the 17..64-row decode GEMMs."""
-        t = self._wpk.get(name)
         w = self.P(name)
-        if t is None or t.device != w.device:
-            if torch.cuda.is_current_stream_capturing():
-                raise ops._lib.VsError("GPT-2 weight copies must exist before a graph capture "
-                                       "(run one eager step first)")
-            t = ops.pack_rows_f32(self._w(name) if transposed else w.detach())
-            self._wpk[name] = t
-        return t
+        return self._copy(self._wpk, name, w,
+                          lambda: ops.pack_rows_f32(self._w(name) if transposed else w.detach()))
 
     def _w(self, name):
         """[out][in] view of a Conv1D weight (transposed once, after load / device move)."""
         w = self.P(name)
-        t = self._wt.get(name)
-        if t is None or t.device != w.device:
-            if torch.cuda.is_current_stream_capturing():
-                raise ops._lib.VsError("GPT-2 weight copies must exist before a graph capture "
-                                       "(run one eager step first)")
-            t = w.detach().t().contiguous()
-            self._wt[name] = t
-        return t
+        return self._copy(self._wt, name, w, lambda: w.detach().t().contiguous())
 
     # ---- compute ---------------------------------------------------------------------------
     def _block(self, i, h, attn_fn):
@@ -295,19 +272,6 @@ class GPT2LMHeadModelHip(nn.Module):
         self._saved = (tokens, km, r, l, layers, h, hf, meanf, rstdf)
         return logits.view(r, l, -1)
 
-    def _grad(self, name):
-        p = self.P(name)
-        if p.grad is None:
-            p.grad = torch.empty_like(p)
-        return p.grad
-
-    def _dense_bwd(self, name, x, dy, need_dx=True):
-        """y = x @ W + b with the Conv1D parameter W [in, out]: dW = x^T dy, db = colsum(dy),
-        dx = dy @ W^T (the parameter itself is the K-contiguous operand of that product)."""
-        ops.gemm_nt(ops.transpose_f32(x), ops.transpose_f32(dy), out=self._grad(name + ".weight"))
-        ops.colsum_f32(dy, out=self._grad(name + ".bias"))
-        return ops.gemm_nt(dy, self.P(name + ".weight")) if need_dx else None
-
     @torch.no_grad()
     def backward(self, dlogits):
         """dlogits [R*L, V] -> .grad of every parameter (overwrite semantics, like the trunk)."""
@@ -325,16 +289,16 @@ class GPT2LMHeadModelHip(nn.Module):
         for i in reversed(range(self.n_layer)):
             q = f"transformer.h.{i}."
             h_in, a, mean1, rstd1, qkv, o, h_mid, m, mean2, rstd2, f_pre, f = layers[i]
-            df = self._dense_bwd(q + "mlp.c_proj", f, dh)
+            df = self._linear_bwd(q + "mlp.c_proj", f, dh, conv1d=True)
             df_pre = ops.gelu_new_bwd(df, f_pre)
-            dm = self._dense_bwd(q + "mlp.c_fc", m, df_pre)
+            dm = self._linear_bwd(q + "mlp.c_fc", m, df_pre, conv1d=True)
             dmid_ln, _, _, _ = ops.add_layernorm_bwd(dm, h_mid, None, self.P(q + "ln_2.weight"), mean2, rstd2,
                                                      dg_out=self._grad(q + "ln_2.weight"),
                                                      db_out=self._grad(q + "ln_2.bias"))
             d_mid = ops.add_f32(dh, dmid_ln)
-            do = self._dense_bwd(q + "attn.c_proj", o, d_mid)
+            do = self._linear_bwd(q + "attn.c_proj", o, d_mid, conv1d=True)
             dqkv = ops.attn_causal_bwd(qkv, km, do, r, l, self.n_head)
-            da = self._dense_bwd(q + "attn.c_attn", a, dqkv)
+            da = self._linear_bwd(q + "attn.c_attn", a, dqkv, conv1d=True)
             din_ln, _, _, _ = ops.add_layernorm_bwd(da, h_in, None, self.P(q + "ln_1.weight"), mean1, rstd1,
                                                     dg_out=self._grad(q + "ln_1.weight"),
                                                     db_out=self._grad(q + "ln_1.bias"))
@@ -343,52 +307,14 @@ class GPT2LMHeadModelHip(nn.Module):
         dwpe = self._grad("transformer.wpe.weight")
         dwpe.zero_()
         ops.gpt2_embed_bwd(tokens, dh, dwte, dwpe)  # adds the embedding rows onto the lm_head gradient
-        self._drop_wt()  # the optimizer is about to change the parameters
-
-    def take_train_state(self):
-        """The activations `forward_train` saved for `backward`, detached from the module (the autograd node keeps
-        them: several forwards may precede a backward)."""
-        st, self._saved = self._saved, None
-        return st
-
-    def put_train_state(self, st):
-        self._saved = st
+        self._drop_copies()  # the optimizer is about to change the parameters
 
     def reorder_state(self, state: KVCacheState, new_order):
         """fairseq reorder_incremental_state: row r of the cache becomes old row new_order[r]."""
-        if state.k is None:
-            return
-        if state.anc is not None:
-            raise ops._lib.VsError("this cache is reordered through its ancestry table (vs_beam_step)")
-        rows = new_order.numel()
-        if state.k2 is None:
-            state.k2, state.v2 = torch.empty_like(state.k), torch.empty_like(state.v)
-        for li in range(self.n_layer):
-            ops.kv_gather(state.k[li], state.k2[li], new_order, state.len)
-            ops.kv_gather(state.v[li], state.v2[li], new_order, state.len)
-        state.k, state.k2 = state.k2, state.k
-        state.v, state.v2 = state.v2, state.v
-        state.rows = rows
+        state.reorder(new_order, self.n_layer)
 
 
-class _GPT2TrainFn(torch.autograd.Function):
-    """One autograd node for the whole language model (manual HIP backward)."""
-
-    @staticmethod
-    def forward(ctx, model, tokens, mask, _tick):
-        ctx.model = model
-        out = model.forward_train(tokens, mask)
-        # the saved activations of THIS forward travel with the node: a second forward before the backward
-        # (two losses, gradient accumulation) must not replace them
-        ctx.saved_state = model.take_train_state() if hasattr(model, "take_train_state") else None
-        return out
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        if ctx.saved_state is not None:
-            ctx.model.put_train_state(ctx.saved_state)
-        ctx.model.backward(dlogits.contiguous())
-        return None, None, None, None
+_GPT2TrainFn = FlatTrainFn  # the name tests/test_gpu_gpt2.py imports
 
 
 class _XentIgnoreFn(torch.autograd.Function):
@@ -434,7 +360,7 @@ class HuggingFaceGPT2Decoder(nn.Module):
         features_mask = prev_output_tokens.ne(self.pad_idx)  # don't attend to padding symbols (:185)
         if self.training and torch.is_grad_enabled():
             tick = torch.zeros(1, device=prev_output_tokens.device, requires_grad=True)
-            return (_GPT2TrainFn.apply(self.model, prev_output_tokens, features_mask, tick),)
+            return (FlatTrainFn.apply(self.model, prev_output_tokens, features_mask, tick),)
         return (self.model.forward_logits(prev_output_tokens, features_mask),)
 
     def reorder_incremental_state(self, incremental_state, new_order):

@@ -14,12 +14,14 @@ the single token-type row, post-LN residual blocks, erf GELU, LayerNorm eps 1e-5
 Stated difference: no dropout anywhere (as in the GPT-2 decoder of this package).
 
 Training: `forward_train` keeps the activations, `backward` is a manual HIP backward behind ONE autograd node
-(`roberta_apply`); parameter gradients are written with overwrite semantics.
+(`roberta_apply` -> `flat_module.FlatTrainFn`); parameter gradients are written with overwrite semantics.  Flat
+registration, the state-dict rules, the fused q/k/v cache's life and the dense-layer backward are `FlatParamModule`'s.
 """
 import torch
 from torch import nn
 
 from . import ops
+from .flat_module import FlatParamModule, FlatTrainFn
 
 ROBERTA_DIMS = {
     # name: dict(n_layer, d_model, n_head, n_positions, vocab, d_ffn, pad, eps)
@@ -30,10 +32,12 @@ ROBERTA_DIMS = {
 }
 
 
-class _RobertaHip(nn.Module):
-    """Parameters under huggingface's names (flat registration, '.' -> '__'), the encoder's forward / backward."""
+class _RobertaHip(FlatParamModule):
+    """Parameters under huggingface's names, the encoder's forward / backward."""
 
     PREFIX = ""
+    _CACHES = ("_qkv",)  # layer -> ([3D][D] weight, [3D] bias, [D][3D] transposed weight): one GEMM for q, k and v
+    _CAPTURE_MSG = "RoBERTa's fused q/k/v weights must exist before a graph capture (run one eager step first)"
 
     def __init__(self, n_layer, d_model, n_head, n_positions, vocab_size, d_ffn, pad_token_id=1, layer_norm_eps=1e-5,
                  add_pooling_layer=True, num_labels=0):
@@ -80,70 +84,31 @@ class _RobertaHip(nn.Module):
             lnorm(q + "output.LayerNorm")
         if self.has_pooler:
             dense("pooler.dense", d_model, d_model)
-        self._names = list(p)
         if self.num_labels:  # RobertaClassificationHead lives beside the encoder, not under its prefix
             for name, (n_out, n_in) in (("classifier.dense", (d_model, d_model)),
                                         ("classifier.out_proj", (self.num_labels, d_model))):
                 p[name + ".weight"] = nn.Parameter(torch.randn(n_out, n_in) * 0.02)
                 p[name + ".bias"] = nn.Parameter(torch.zeros(n_out))
-            self._names = list(p)
-        for k, v in p.items():
-            self.register_parameter(k.replace(".", "__"), v)
-        self._qkv = {}  # layer -> ([3D][D] weight, [3D] bias, [D][3D] transposed weight): one GEMM for q, k and v
-        self._saved = None
+        self._register_flat(p)
 
     # ---- huggingface-compatible state dict -------------------------------------------------
-    def P(self, name):
-        return getattr(self, name.replace(".", "__"))
-
     def E(self, name):
         """A parameter of the encoder (under the model's prefix)."""
         return self.P(self.PREFIX + name)
 
-    def _save_to_state_dict(self, destination, prefix, keep_vars):
-        for k in self._names:
-            v = self.P(k)
-            destination[prefix + k] = v if keep_vars else v.detach()
-
-    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
-                              error_msgs):
-        mine = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
-        with torch.no_grad():
-            for k in self._names:
-                if k in mine:
-                    src = torch.as_tensor(mine[k])
-                    if src.shape != self.P(k).shape:
-                        error_msgs.append(f"size mismatch for {prefix + k}: {tuple(src.shape)} vs "
-                                          f"{tuple(self.P(k).shape)}")
-                    else:
-                        self.P(k).copy_(src)
-                else:
-                    missing_keys.append(prefix + k)
-        for k in mine:
-            # checkpoints of the pinned release carry the position-id buffer; newer releases dropped it
-            if k not in self._names and not k.endswith("embeddings.position_ids"):
-                unexpected_keys.append(prefix + k)
-        self._drop_wt()
-
-    def _drop_wt(self):
-        self._qkv.clear()
-
-    def _apply(self, fn, *args, **kwargs):
-        self._qkv.clear()  # device / dtype moves replace the parameters' storage
-        return super()._apply(fn, *args, **kwargs)
+    def _tolerated_on_load(self, key):
+        # checkpoints of the pinned release carry the position-id buffer; newer releases dropped it
+        return key.endswith("embeddings.position_ids")
 
     def _fused_qkv(self, i):
-        t = self._qkv.get(i)
         q = f"encoder.layer.{i}.attention.self."
-        if t is None or t[0].device != self.E(q + "query.weight").device:
-            if torch.cuda.is_current_stream_capturing():
-                raise ops._lib.VsError("RoBERTa's fused q/k/v weights must exist before a graph capture "
-                                       "(run one eager step first)")
+
+        def make():
             w = torch.cat([self.E(q + s + ".weight").detach() for s in ("query", "key", "value")], 0).contiguous()
             b = torch.cat([self.E(q + s + ".bias").detach() for s in ("query", "key", "value")], 0).contiguous()
-            t = (w, b, ops.transpose_f32(w))
-            self._qkv[i] = t
-        return t
+            return w, b, ops.transpose_f32(w)
+
+        return self._copy(self._qkv, i, self.E(q + "query.weight"), make)
 
     # ---- compute ---------------------------------------------------------------------------
     def _check(self, tokens, attention_mask):
@@ -192,38 +157,23 @@ class _RobertaHip(nn.Module):
     def _first_token(self, h, r, l):
         return h.view(r, l, self.d_model)[:, 0].contiguous()
 
-    def _grad(self, name):
-        p = self.E(name) if not name.startswith("classifier.") else self.P(name)
-        if p.grad is None:
-            p.grad = torch.empty_like(p)
-        return p.grad
-
-    def _dense_bwd(self, name, x, dy, need_dx=True):
-        """y = x W^T + b, W [out, in]: dW = dy^T x, db = colsum(dy), dx = dy W."""
-        ops.gemm_nt(ops.transpose_f32(dy), ops.transpose_f32(x), out=self._grad(name + ".weight"))
-        ops.colsum_f32(dy, out=self._grad(name + ".bias"))
-        if not need_dx:
-            return None
-        w = self.E(name + ".weight") if not name.startswith("classifier.") else self.P(name + ".weight")
-        return ops.gemm_nt(dy, ops.transpose_f32(w))
-
     def _encode_bwd(self, saved, dh):
         """dh [R*L, D]: gradient of the last hidden state -> every encoder / embedding parameter's .grad."""
         tokens, pos_ids, km, r, l, e, mean0, rstd0, layers = saved
-        d = self.d_model
+        d, pre = self.d_model, self.PREFIX  # parameters by their full names from here on
         for i in reversed(range(self.n_layer)):
-            q = f"encoder.layer.{i}."
+            q = f"{pre}encoder.layer.{i}."
             h_in, qkv, ctx, ao, mean1, rstd1, h1, f_pre, f, fo, mean2, rstd2 = layers[i]
-            ds2 = ops.add_layernorm_bwd(dh, fo, h1, self.E(q + "output.LayerNorm.weight"), mean2, rstd2,
+            ds2 = ops.add_layernorm_bwd(dh, fo, h1, self.P(q + "output.LayerNorm.weight"), mean2, rstd2,
                                         dg_out=self._grad(q + "output.LayerNorm.weight"),
                                         db_out=self._grad(q + "output.LayerNorm.bias"))[0]
-            df = self._dense_bwd(q + "output.dense", f, ds2)
+            df = self._linear_bwd(q + "output.dense", f, ds2)
             df_pre = ops.gelu_erf_bwd(df, f_pre)
-            dh1 = ops.add_f32(self._dense_bwd(q + "intermediate.dense", h1, df_pre), ds2)
-            ds1 = ops.add_layernorm_bwd(dh1, ao, h_in, self.E(q + "attention.output.LayerNorm.weight"), mean1, rstd1,
+            dh1 = ops.add_f32(self._linear_bwd(q + "intermediate.dense", h1, df_pre), ds2)
+            ds1 = ops.add_layernorm_bwd(dh1, ao, h_in, self.P(q + "attention.output.LayerNorm.weight"), mean1, rstd1,
                                         dg_out=self._grad(q + "attention.output.LayerNorm.weight"),
                                         db_out=self._grad(q + "attention.output.LayerNorm.bias"))[0]
-            dctx = self._dense_bwd(q + "attention.output.dense", ctx, ds1)
+            dctx = self._linear_bwd(q + "attention.output.dense", ctx, ds1)
             dqkv = ops.attn_pad_bwd(qkv, km, dctx, r, l, self.n_head)
             # the fused projection: weight gradients straight into the three separate parameters
             _, _, wt = self._fused_qkv(i)
@@ -234,25 +184,18 @@ class _RobertaHip(nn.Module):
                 self._grad(q + "attention.self." + nm + ".bias").copy_(db[s * d:(s + 1) * d])
             dh = ops.add_f32(ops.gemm_nt(dqkv, wt), ds1)
             layers[i] = None
-        de = ops.add_layernorm_bwd(dh, e, None, self.E("embeddings.LayerNorm.weight"), mean0, rstd0,
-                                   dg_out=self._grad("embeddings.LayerNorm.weight"),
-                                   db_out=self._grad("embeddings.LayerNorm.bias"))[0]
-        dword = self._grad("embeddings.word_embeddings.weight")
-        dpos = self._grad("embeddings.position_embeddings.weight")
+        de = ops.add_layernorm_bwd(dh, e, None, self.P(pre + "embeddings.LayerNorm.weight"), mean0, rstd0,
+                                   dg_out=self._grad(pre + "embeddings.LayerNorm.weight"),
+                                   db_out=self._grad(pre + "embeddings.LayerNorm.bias"))[0]
+        dword = self._grad(pre + "embeddings.word_embeddings.weight")
+        dpos = self._grad(pre + "embeddings.position_embeddings.weight")
         dword.zero_()
         dpos.zero_()
         # both tables have padding_idx = pad: vs_embed_scatter_bwd skips those rows
         ops.embed_scatter_bwd(tokens, de, dword, 1.0, self.pad)
         ops.embed_scatter_bwd(pos_ids, de, dpos, 1.0, self.pad)
-        ops.colsum_f32(de, out=self._grad("embeddings.token_type_embeddings.weight").view(-1))
-        self._drop_wt()  # the optimizer is about to change the parameters
-
-    def take_train_state(self):
-        st, self._saved = self._saved, None
-        return st
-
-    def put_train_state(self, st):
-        self._saved = st
+        ops.colsum_f32(de, out=self._grad(pre + "embeddings.token_type_embeddings.weight").view(-1))
+        self._drop_copies()  # the optimizer is about to change the parameters
 
 
 class RobertaModelHip(_RobertaHip):
@@ -296,7 +239,7 @@ class RobertaModelHip(_RobertaHip):
             dh = torch.zeros((r * l, self.d_model), dtype=torch.float32, device=saved[0].device)
         if dpooled is not None and self.has_pooler:
             dpre = ops.tanh_bwd(dpooled.contiguous(), pooled)
-            dx0 = self._dense_bwd("pooler.dense", x0, dpre)
+            dx0 = self._linear_bwd(self.PREFIX + "pooler.dense", x0, dpre)
             dh.view(r, l, self.d_model)[:, 0] += dx0
         self._encode_bwd(saved, dh)
 
@@ -333,8 +276,8 @@ class RobertaForSequenceClassificationHip(_RobertaHip):
         saved, x0, c1 = self._saved
         self._saved = None
         r, l = saved[3], saved[4]
-        dc1 = self._dense_bwd("classifier.out_proj", c1, dlogits.contiguous())
-        dx0 = self._dense_bwd("classifier.dense", x0, ops.tanh_bwd(dc1, c1))
+        dc1 = self._linear_bwd("classifier.out_proj", c1, dlogits.contiguous())
+        dx0 = self._linear_bwd("classifier.dense", x0, ops.tanh_bwd(dc1, c1))
         dh = torch.zeros((r * l, self.d_model), dtype=torch.float32, device=dx0.device)
         dh.view(r, l, self.d_model)[:, 0] = dx0
         self._encode_bwd(saved, dh)
@@ -346,32 +289,11 @@ class _Out(dict):
     __getattr__ = dict.get
 
 
-class _RobertaTrainFn(torch.autograd.Function):
-    """One autograd node for the whole encoder (manual HIP backward); the saved activations travel with the node."""
-
-    @staticmethod
-    def forward(ctx, model, tokens, mask, _tick):
-        ctx.model = model
-        ctx.set_materialize_grads(False)  # an output nobody used arrives as None, not as a tensor of zeros
-        outs = model.forward_train(tokens, mask)
-        ctx.saved_state = model.take_train_state()
-        ctx.present = [o is not None for o in outs]
-        return tuple(o for o in outs if o is not None)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        it = iter(grads)
-        full = [next(it) if present else None for present in ctx.present]
-        ctx.model.put_train_state(ctx.saved_state)
-        ctx.model.backward(*[g.contiguous() if g is not None else None for g in full])
-        return None, None, None, None
-
-
 def roberta_apply(model, tokens, mask):
     """The model's outputs as tensors autograd can differentiate through (training), or the plain forward's."""
     if model.training and torch.is_grad_enabled():
         tick = torch.zeros(1, device=tokens.device, requires_grad=True)
-        return _RobertaTrainFn.apply(model, tokens, mask, tick)
+        return FlatTrainFn.apply(model, tokens, mask, tick)
     with torch.no_grad():
         outs = model._outputs(tokens, mask, keep=False)
     return tuple(o for o in outs if o is not None)

@@ -22,8 +22,8 @@ from torch import nn
 from . import ops
 from .trunk import RawFrames, VideoTrunk
 from .transformer_code import Transformer as TxCodeEnc, LinearFn
-from .hf_gpt2_fseq import (GPT2_DIMS, GPT2LMHeadModelHip, HuggingFaceGPT2Decoder, _GPT2TrainFn,
-                           lm_loss as gpt2_lm_loss)
+from .flat_module import FlatTrainFn
+from .hf_gpt2_fseq import GPT2_DIMS, GPT2LMHeadModelHip, HuggingFaceGPT2Decoder, lm_loss as gpt2_lm_loss
 from .fseq_txdec import TxDecoderReal, TxEncoderOld
 
 EncoderOut = namedtuple(
@@ -347,7 +347,7 @@ class Simple_GPT2(nn.Module):
         keep = _first_annotation(inp["seq_out_lens_by_ev"]).ne(0)
         if self.training and torch.is_grad_enabled():
             tick = torch.zeros(1, device=toks.device, requires_grad=True)
-            logits = _GPT2TrainFn.apply(self.gpt2_mdl, toks, keep, tick)
+            logits = FlatTrainFn.apply(self.gpt2_mdl, toks, keep, tick)
         else:
             logits = self.gpt2_mdl.forward_logits(toks, keep)
         return {"loss": gpt2_lm_loss(logits, toks, self.pad_index), "logits": logits}

@@ -651,6 +651,39 @@ int vs_xent_ignore_grad_dev(const float* logits, const int64_t* labels, const fl
                             float* dlogits, int rows, int V, int64_t ld, int ignore_index,
                             const float* grad_scale_dev, void* stream);
 
+/* ---- Train-mode dropout from an in-kernel counter generator (csrc/dropout_rng.h: Philox4x32-10, shared by host and
+ * device code).  A mask is a function of (seed, step, site, element index) and is never stored: the kernel that
+ * applies it and the kernel that differentiates through it both compute it.
+ *   key = (seed low 32, seed high 32); counter = (b low 32, b high 32, site, step low 32) with b = e >> 2, element e
+ *   takes word e & 3 of that block; keep iff word >= thr, thr = (uint32) floor(p * 2^32 + 0.5); kept elements are
+ *   multiplied by scale = 1 / (1 - p).
+ * vs_dropout_threshold computes (thr, scale) from p in double and refuses p outside 0 <= p < 1 (VS_ERR_BAD_ARG);
+ * every kernel below takes that pair.  `snap` is device memory, int64 [seed, step]: vs_dropout_tick copies the
+ * persistent `state` [seed, step] into it and adds 1 to state's step (one thread; the only launch that writes the
+ * state, captured with the training step so that every replay of a hipGraph draws its own masks).
+ * vs_dropout_mask_host: keep[i] = mask of element e0 + i, on the host (no GPU), for C callers and tests. */
+int vs_dropout_threshold(double p, uint32_t* thr, float* scale);
+int vs_dropout_mask_host(uint64_t seed, uint64_t step, uint32_t site, uint64_t e0, int64_t n, uint32_t thr,
+                         uint8_t* keep);
+int vs_dropout_tick(int64_t* state, int64_t* snap, void* stream);
+/* out = res + m * x over n floats (res may be NULL), element index = position in the array.  Four elements and one
+ * Philox block per thread with 16-byte accesses; n % 4 != 0 or a pointer off the 16-byte grid takes a scalar kernel.
+ * Forward of a residual site (res = the residual stream) and its backward (res = NULL, x = the incoming gradient). */
+int vs_dropout_add_f32(const float* x, const float* res, float* out, int64_t n, const int64_t* snap, uint32_t site,
+                       uint32_t thr, float scale, void* stream);
+/* vs_gpt2_embed with dropout on wte + wpe before the store; element index = the flat index in [R*L, D]. */
+int vs_gpt2_embed_drop(const int64_t* tokens, const float* wte, const float* wpe, float* out, int R, int L, int D,
+                       int pos0, int V, const int64_t* snap, uint32_t site, uint32_t thr, float scale, void* stream);
+/* vs_attn_causal_fwd / _bwd with dropout on the attention probabilities: out_i = sum_j p_ij m_ij v_j (the softmax is
+ * normalised before the mask).  Element index of (r, h, i, j) = ((r*H + h)*L + i)*Lp + j with Lp = (L + 3) & ~3.  The
+ * same kernels as the plain entry points (one template, which those instantiate without the mask); the backward uses
+ * the plain entry point's scratch size; with thr = 0, scale = 1 the results equal the plain ones bit for bit. */
+int vs_attn_causal_drop_fwd(const float* qkv, const uint8_t* key_mask, float* out, int R, int L, int H, int dh,
+                            const int64_t* snap, uint32_t site, uint32_t thr, float scale, void* stream);
+int vs_attn_causal_drop_bwd(const float* qkv, const uint8_t* key_mask, const float* dout, float* dqkv, void* scratch,
+                            size_t scratch_bytes, int R, int L, int H, int dh, const int64_t* snap, uint32_t site,
+                            uint32_t thr, float scale, void* stream);
+
 /* Device-side beam-search bookkeeping of one step (SeqGenCustom._generate between two decoder
  * calls, seq_gen.py:368-520, and finalize_hypos :579-697), one block per sentence, no host sync:
  * merges the per-row lists of vs_beam_topk (k = min(2*beam, V-1) entries each) into the reference's

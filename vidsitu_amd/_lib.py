@@ -71,6 +71,7 @@ class WgradItem(C.Structure):
 
 
 _p, _i, _i64, _f, _d, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
+_u32, _u64 = C.c_uint32, C.c_uint64
 _dp = C.POINTER(ConvDesc)
 
 # name -> (restype, argtypes); mirrors include/vidsitu_hip.h one to one
@@ -200,6 +201,13 @@ SIGNATURES = {
     "vs_gpt2_embed_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "vs_xent_ignore_grad": (_i, [_p, _p, _p, _p, _i, _i, _i64, _i, _f, _p]),
     "vs_xent_ignore_grad_dev": (_i, [_p, _p, _p, _p, _i, _i, _i64, _i, _p, _p]),
+    "vs_dropout_threshold": (_i, [_d, C.POINTER(_u32), C.POINTER(_f)]),
+    "vs_dropout_mask_host": (_i, [_u64, _u64, _u32, _u64, _i64, _u32, _p]),
+    "vs_dropout_tick": (_i, [_p, _p, _p]),
+    "vs_dropout_add_f32": (_i, [_p, _p, _p, _i64, _p, _u32, _u32, _f, _p]),
+    "vs_gpt2_embed_drop": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _u32, _u32, _f, _p]),
+    "vs_attn_causal_drop_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _u32, _u32, _f, _p]),
+    "vs_attn_causal_drop_bwd": (_i, [_p, _p, _p, _p, _p, _sz, _i, _i, _i, _i, _p, _u32, _u32, _f, _p]),
     "vs_attn_pad_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "vs_attn_pad_bwd_scratch_bytes": (_sz, [_i, _i, _i]),
     "vs_attn_pad_bwd": (_i, [_p, _p, _p, _p, _p, _sz, _i, _i, _i, _i, _p]),

@@ -8,6 +8,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "dropout_rng.h"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
@@ -237,8 +238,17 @@ extern "C" int vs_gemm_nt_f32_ws(const float* x, const float* w, const float* b,
 // ----------------------------------------------------------------------------
 // h[r, l, :] = wte[tok[r, l]] + wpe[pos0 + l]      (GPT2Model: default position ids)
 // ----------------------------------------------------------------------------
+// DROP: the embedding dropout on wte + wpe before the store; element index = the flat index in [R*L, D], so the four
+// floats of a thread are one Philox block.
+struct DropArgs {
+  const int64_t* snap;  // [seed, step] of this step (vs_dropout_tick)
+  uint32_t site, thr;
+  float scale;
+};
+
+template <bool DROP>
 __global__ void gpt2_embed_kernel(const int64_t* tok, const float* wte, const float* wpe, float* out,
-                                  int rows, int L, int D, int pos0, int V) {
+                                  int rows, int L, int D, int pos0, int V, DropArgs dr) {
   const int row = blockIdx.x;  // r * L + l
   const int l = row % L;
   long long t = tok[row];
@@ -248,15 +258,34 @@ __global__ void gpt2_embed_kernel(const int64_t* tok, const float* wte, const fl
   float4* o = (float4*)(out + (long long)row * D);
   for (int i = threadIdx.x; i < D / 4; i += blockDim.x) {
     const float4 u = a[i], v = p[i];
-    o[i] = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
+    float4 y = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
+    if (DROP) {
+      const vs_philox_out w = vs_dropout_block((uint64_t)dr.snap[0], (uint64_t)dr.snap[1], dr.site,
+                                               (uint64_t)row * (uint64_t)(D / 4) + (uint64_t)i);
+      y.x = w.w[0] >= dr.thr ? y.x * dr.scale : 0.f;
+      y.y = w.w[1] >= dr.thr ? y.y * dr.scale : 0.f;
+      y.z = w.w[2] >= dr.thr ? y.z * dr.scale : 0.f;
+      y.w = w.w[3] >= dr.thr ? y.w * dr.scale : 0.f;
+    }
+    o[i] = y;
   }
 }
 
 extern "C" int vs_gpt2_embed(const int64_t* tokens, const float* wte, const float* wpe, float* out,
                              int R, int L, int D, int pos0, int V, void* stream) {
   VS_CHECK_ARG(tokens && wte && wpe && out && R > 0 && L > 0 && D % 4 == 0, "bad args");
-  hipLaunchKernelGGL(gpt2_embed_kernel, dim3(R * L), dim3(256), 0, (hipStream_t)stream, tokens, wte,
-                     wpe, out, R * L, L, D, pos0, V);
+  hipLaunchKernelGGL(gpt2_embed_kernel<false>, dim3(R * L), dim3(256), 0, (hipStream_t)stream, tokens, wte,
+                     wpe, out, R * L, L, D, pos0, V, DropArgs{});
+  VS_CHECK_LAUNCH();
+  return VS_OK;
+}
+
+extern "C" int vs_gpt2_embed_drop(const int64_t* tokens, const float* wte, const float* wpe, float* out,
+                                  int R, int L, int D, int pos0, int V, const int64_t* snap, uint32_t site,
+                                  uint32_t thr, float scale, void* stream) {
+  VS_CHECK_ARG(tokens && wte && wpe && out && snap && R > 0 && L > 0 && D % 4 == 0, "bad args");
+  hipLaunchKernelGGL(gpt2_embed_kernel<true>, dim3(R * L), dim3(256), 0, (hipStream_t)stream, tokens, wte,
+                     wpe, out, R * L, L, D, pos0, V, DropArgs{snap, site, thr, scale});
   VS_CHECK_LAUNCH();
   return VS_OK;
 }
@@ -271,8 +300,29 @@ extern "C" int vs_gpt2_embed(const int64_t* tokens, const float* wte, const floa
 // Grid = (r, head) x chunks of AC_QC queries: 160 blocks of 60 queries each were a latency-bound launch
 // (91 us per layer); a chunk's block loads the K rows up to its last query and all V rows.
 #define AC_QC 16
+
+// Dropout on one query's row of attention probabilities, in LDS, by the wave that owns the row: row[j] becomes
+// MUL ? row[j] * m_j : m_j with m_j = scale or 0.  Element index = rowblk * 4 + j where rowblk * 4 =
+// ((r * H + h) * L + i) * Lp and Lp = (L + 3) & ~3: the padded pitch puts four consecutive keys of a query into one
+// Philox block, so a lane draws one block for its four keys (one block per key was the alternative; this form does
+// a quarter of the integer multiplies, and rows of up to 256 keys take one pass).
+template <bool MUL>
+__device__ __forceinline__ void drop_row(float* row, int L, uint64_t rowblk, const DropArgs& dr, int lane) {
+  const uint64_t seed = (uint64_t)dr.snap[0], step = (uint64_t)dr.snap[1];
+  for (int j4 = lane * 4; j4 < L; j4 += 256) {
+    const vs_philox_out w = vs_dropout_block(seed, step, dr.site, rowblk + (uint64_t)(j4 >> 2));
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (j4 + k < L) {
+        const float m = w.w[k] >= dr.thr ? dr.scale : 0.f;
+        row[j4 + k] = MUL ? row[j4 + k] * m : m;
+      }
+  }
+}
+
+template <bool DROP>
 __global__ __launch_bounds__(256) void attn_causal_kernel(const float* qkv, const uint8_t* kmask,
-                                                          float* out, int L, int H, int dh) {
+                                                          float* out, int L, int H, int dh, DropArgs dr) {
   extern __shared__ float sm[];
   const int D = H * dh, ld = dh + 1;
   const int r = blockIdx.x / H, h = blockIdx.x % H;
@@ -316,6 +366,10 @@ __global__ __launch_bounds__(256) void attn_causal_kernel(const float* qkv, cons
     }
     sum = wave_reduce_sum(sum);
     __builtin_amdgcn_wave_barrier();
+    if (DROP) {  // out_i = sum_j p_ij m_ij v_j: the row sum above is the undropped one
+      drop_row<true>(P, L, ((uint64_t)blockIdx.x * L + i) * (uint64_t)((L + 3) >> 2), dr, lane);
+      __builtin_amdgcn_wave_barrier();
+    }
     const float inv = 1.0f / sum;
     for (int d = lane; d < dh; d += 64) {
       float o = 0.f;
@@ -326,21 +380,34 @@ __global__ __launch_bounds__(256) void attn_causal_kernel(const float* qkv, cons
   }
 }
 
-extern "C" int vs_attn_causal_fwd(const float* qkv, const uint8_t* key_mask, float* out, int R, int L,
-                                  int H, int dh, void* stream) {
+template <bool DROP>
+static int attn_causal_fwd_launch(const float* qkv, const uint8_t* key_mask, float* out, int R, int L, int H,
+                                  int dh, DropArgs dr, void* stream) {
   VS_CHECK_ARG(qkv && out && R > 0 && L > 0 && H > 0 && dh > 0, "bad args");
   const size_t smem = ((size_t)2 * L * (dh + 1) + 4 * L + 4 * dh) * sizeof(float);
   VS_CHECK_ARG(smem <= 160 * 1024, "sequence too long for the LDS-resident attention (L*dh)");
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)attn_causal_kernel,
+    (void)hipFuncSetAttribute((const void*)attn_causal_kernel<DROP>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
-  hipLaunchKernelGGL(attn_causal_kernel, dim3(R * H, (L + AC_QC - 1) / AC_QC), dim3(256), smem,
-                     (hipStream_t)stream, qkv, key_mask, out, L, H, dh);
+  hipLaunchKernelGGL(attn_causal_kernel<DROP>, dim3(R * H, (L + AC_QC - 1) / AC_QC), dim3(256), smem,
+                     (hipStream_t)stream, qkv, key_mask, out, L, H, dh, dr);
   VS_CHECK_LAUNCH();
   return VS_OK;
+}
+
+extern "C" int vs_attn_causal_fwd(const float* qkv, const uint8_t* key_mask, float* out, int R, int L,
+                                  int H, int dh, void* stream) {
+  return attn_causal_fwd_launch<false>(qkv, key_mask, out, R, L, H, dh, DropArgs{}, stream);
+}
+
+extern "C" int vs_attn_causal_drop_fwd(const float* qkv, const uint8_t* key_mask, float* out, int R, int L,
+                                       int H, int dh, const int64_t* snap, uint32_t site, uint32_t thr,
+                                       float scale, void* stream) {
+  VS_CHECK_ARG(snap, "bad args");
+  return attn_causal_fwd_launch<true>(qkv, key_mask, out, R, L, H, dh, DropArgs{snap, site, thr, scale}, stream);
 }
 
 // ----------------------------------------------------------------------------
@@ -1082,9 +1149,14 @@ extern "C" int vs_colsum_f32(const float* x, float* out, int M, int N, void* str
 // dV_j = sum_i p_ij dO_i, the chunk's P / dS columns staged in LDS -- every output has one owner, fixed
 // summation order, no atomics.
 // ----------------------------------------------------------------------------
+// DROP (out_i = sum_j p_ij m_ij v_j, the mask regenerated from the step's snapshot): launch A has
+// dP_ij = m_ij (dO_i . V_j) and writes p_ij m_ij where it writes p_ij, so launch B's dV_j = sum_i (p m)_ij dO_i is
+// the same code reading it.
+template <bool DROP>
 __global__ __launch_bounds__(256) void attn_causal_bwd_q_kernel(const float* qkv, const uint8_t* kmask,
                                                                 const float* dout, float* dqkv,
-                                                                float* scratch, int L, int H, int dh) {
+                                                                float* scratch, int L, int H, int dh,
+                                                                DropArgs dr) {
   extern __shared__ float sm[];
   const int D = H * dh, ld = dh + 1;
   const int r = blockIdx.x / H, h = blockIdx.x % H;
@@ -1139,10 +1211,19 @@ __global__ __launch_bounds__(256) void attn_causal_bwd_q_kernel(const float* qkv
     sum = wave_reduce_sum(sum);
     const float inv = 1.0f / sum;
     float dsum = 0.f;
+    if (DROP) {  // sw = the row's mask m_i. (0 or 1 / (1 - p))
+      drop_row<false>(sw, L, ((uint64_t)blockIdx.x * L + i) * (uint64_t)((L + 3) >> 2), dr, lane);
+      __builtin_amdgcn_wave_barrier();
+    }
     for (int j = lane; j < L; j += 64) {
       const float pj = pw[j] * inv;
       float dp = 0.f;
       for (int d = 0; d < dh; ++d) dp += oi[d] * Vs[j * ld + d];
+      if (DROP) {
+        const float m = sw[j];
+        dp *= m;
+        P[(long long)i * L + j] = pj * m;
+      }
       pw[j] = pj;
       sw[j] = dp;
       dsum += pj * dp;
@@ -1151,7 +1232,7 @@ __global__ __launch_bounds__(256) void attn_causal_bwd_q_kernel(const float* qkv
     for (int j = lane; j < L; j += 64) {
       const float ds = pw[j] * (sw[j] - dsum);
       sw[j] = ds;
-      P[(long long)i * L + j] = pw[j];
+      if (!DROP) P[(long long)i * L + j] = pw[j];
       dS[(long long)i * L + j] = ds;
     }
     __builtin_amdgcn_wave_barrier();
@@ -1209,9 +1290,10 @@ extern "C" size_t vs_attn_causal_bwd_scratch_bytes(int R, int L, int H) {
   return (size_t)R * H * 2 * L * L * sizeof(float);
 }
 
-extern "C" int vs_attn_causal_bwd(const float* qkv, const uint8_t* key_mask, const float* dout,
-                                  float* dqkv, void* scratch, size_t scratch_bytes, int R, int L, int H,
-                                  int dh, void* stream) {
+template <bool DROP>
+static int attn_causal_bwd_launch(const float* qkv, const uint8_t* key_mask, const float* dout, float* dqkv,
+                                  void* scratch, size_t scratch_bytes, int R, int L, int H, int dh, DropArgs dr,
+                                  void* stream) {
   VS_CHECK_ARG(qkv && dout && dqkv && scratch && R > 0 && L > 0 && H > 0 && dh > 0, "bad args");
   VS_CHECK_ARG(scratch_bytes >= vs_attn_causal_bwd_scratch_bytes(R, L, H), "scratch too small");
   const size_t smem_q = ((size_t)(2 * L + 2 * AC_QC) * (dh + 1) + 8 * L) * sizeof(float);
@@ -1220,19 +1302,35 @@ extern "C" int vs_attn_causal_bwd(const float* qkv, const uint8_t* key_mask, con
                "sequence too long for the LDS-resident attention backward");
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)attn_causal_bwd_q_kernel,
+    (void)hipFuncSetAttribute((const void*)attn_causal_bwd_q_kernel<DROP>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)attn_causal_bwd_kv_kernel,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
   const dim3 grid(R * H, (L + AC_QC - 1) / AC_QC);
-  hipLaunchKernelGGL(attn_causal_bwd_q_kernel, grid, dim3(256), smem_q, (hipStream_t)stream, qkv, key_mask,
-                     dout, dqkv, (float*)scratch, L, H, dh);
+  hipLaunchKernelGGL(attn_causal_bwd_q_kernel<DROP>, grid, dim3(256), smem_q, (hipStream_t)stream, qkv, key_mask,
+                     dout, dqkv, (float*)scratch, L, H, dh, dr);
   hipLaunchKernelGGL(attn_causal_bwd_kv_kernel, grid, dim3(256), smem_kv, (hipStream_t)stream, qkv, dout, dqkv,
                      (const float*)scratch, L, H, dh);
   VS_CHECK_LAUNCH();
   return VS_OK;
+}
+
+extern "C" int vs_attn_causal_bwd(const float* qkv, const uint8_t* key_mask, const float* dout,
+                                  float* dqkv, void* scratch, size_t scratch_bytes, int R, int L, int H,
+                                  int dh, void* stream) {
+  return attn_causal_bwd_launch<false>(qkv, key_mask, dout, dqkv, scratch, scratch_bytes, R, L, H, dh, DropArgs{},
+                                       stream);
+}
+
+extern "C" int vs_attn_causal_drop_bwd(const float* qkv, const uint8_t* key_mask, const float* dout,
+                                       float* dqkv, void* scratch, size_t scratch_bytes, int R, int L, int H,
+                                       int dh, const int64_t* snap, uint32_t site, uint32_t thr, float scale,
+                                       void* stream) {
+  VS_CHECK_ARG(snap, "bad args");
+  return attn_causal_bwd_launch<true>(qkv, key_mask, dout, dqkv, scratch, scratch_bytes, R, L, H, dh,
+                                      DropArgs{snap, site, thr, scale}, stream);
 }
 
 // Embedding backward: dwte[tok] += dh, dwpe[pos0 + l] += dh (fp32 atomics: several rows may hit the

@@ -155,7 +155,11 @@ class CfgProcessor:
         self.cfg_pth = cfg_pth
 
     def get_vsitu_default_cfg(self):
-        return CfgNode(_load_yaml(self.cfg_pth))
+        cfg = CfgNode(_load_yaml(self.cfg_pth))
+        # an addition of this project that the reference's own config file does not carry: that file still loads,
+        # and the key can be overridden on top of it
+        cfg.mdl.setdefault("gpt2_dropout", 0.0)
+        return cfg
 
     @staticmethod
     def update_one_full_key(cfg, full_key, v):

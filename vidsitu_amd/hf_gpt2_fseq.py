@@ -15,6 +15,13 @@ re-encodes the whole prefix every step.  The same call with
 `incremental_state=None` does that here; given a `KVCacheState` the decoder appends one position to
 a KV cache instead -- identical arithmetic, one token of work per step.
 
+Dropout: huggingface's GPT-2 defaults (`embd_pdrop = attn_pdrop = resid_pdrop = 0.1`) are what the reference trains
+with (its own overrides at `:144-146` are commented out).  Here the three probabilities are constructor arguments,
+0 by default; above 0 the train-mode pass applies the masks of transformers 3.3.1's four dropout sites from the
+counter generator of csrc/dropout_rng.h inside the kernels (nothing is stored: the backward regenerates them from the
+step's snapshot of the persistent `[seed, step]` device state).  Eval, `forward_logits`, `forward_step` and generation
+never apply dropout and never advance the state.
+
 `GPT2LMHeadModelHip` is a `flat_module.FlatParamModule`: registration, state dict, the cached weight copies and the
 autograd node (`FlatTrainFn`) live there; this file keeps the names / shapes, the arithmetic and `KVCacheState`.
 """
@@ -69,9 +76,17 @@ class GPT2LMHeadModelHip(FlatParamModule):
                "_wpk")  # fragment-major copies for the decode-step GEMMs (ops.gemm_nt_packed)
     _CAPTURE_MSG = "GPT-2 weight copies must exist before a graph capture (run one eager step first)"
 
-    def __init__(self, n_layer, d_model, n_head, n_positions, vocab_size):
+    _DROP_CAPTURE_MSG = "the GPT-2 dropout state must exist before a graph capture (run one eager step first)"
+
+    def __init__(self, n_layer, d_model, n_head, n_positions, vocab_size, embd_pdrop=0.0, attn_pdrop=0.0,
+                 resid_pdrop=0.0):
         super().__init__()
         self.n_layer, self.d_model, self.n_head, self.n_positions = n_layer, d_model, n_head, n_positions
+        self.embd_pdrop, self.attn_pdrop, self.resid_pdrop = float(embd_pdrop), float(attn_pdrop), float(resid_pdrop)
+        # (thr, scale) per probability, None at p = 0 (that site then runs today's launches); refuses p outside [0, 1)
+        self._drop_embd, self._drop_attn, self._drop_resid = (
+            ops.dropout_params(p) if p != 0.0 else None for p in (embd_pdrop, attn_pdrop, resid_pdrop))
+        self._drop_state = None  # i64 [seed, step] on the device: not a parameter, not in the state dict
         self.config = type("Cfg", (), {"n_positions": n_positions, "n_embd": d_model,
                                        "n_layer": n_layer, "n_head": n_head,
                                        "vocab_size": vocab_size})()
@@ -132,6 +147,45 @@ class GPT2LMHeadModelHip(FlatParamModule):
         """[out][in] view of a Conv1D weight (transposed once, after load / device move)."""
         w = self.P(name)
         return self._copy(self._wt, name, w, lambda: w.detach().t().contiguous())
+
+    # ---- dropout state -----------------------------------------------------------------------
+    def _dropout_on(self):
+        return not (self._drop_embd is None and self._drop_attn is None and self._drop_resid is None)
+
+    def _drop_state_on(self, device):
+        """The persistent [seed, step] buffer on `device`; the seed is drawn from torch's default CPU generator at the
+        first train-mode forward (so `torch.manual_seed` governs it)."""
+        st = self._drop_state
+        if st is None or st.device != device:
+            if torch.cuda.is_current_stream_capturing():
+                raise ops._lib.VsError(self._DROP_CAPTURE_MSG)
+            if st is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64))
+                st = torch.tensor([seed, 0], dtype=torch.int64)
+            st = self._drop_state = st.to(device)
+        return st
+
+    def dropout_state(self):
+        """(seed, step) of the next train-mode forward, or None before the first one."""
+        if self._drop_state is None:
+            return None
+        seed, step = self._drop_state.tolist()
+        return seed, step
+
+    def set_dropout_state(self, state):
+        """Continue from `(seed, step)` (what `dropout_state()` returned).  Written in place when the buffer exists:
+        captured training steps keep reading the same memory."""
+        new = torch.tensor([int(state[0]), int(state[1])], dtype=torch.int64)
+        if self._drop_state is None:
+            self._drop_state = new.to(self.P("transformer.wte.weight").device)
+        else:
+            self._drop_state.copy_(new)
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        if self._drop_state is not None:  # the state moves with .to(); it stays int64 under a dtype cast
+            self._drop_state = self._drop_state.to(self.P("transformer.wte.weight").device)
+        return out
 
     # ---- compute ---------------------------------------------------------------------------
     def _block(self, i, h, attn_fn):
@@ -250,32 +304,47 @@ class GPT2LMHeadModelHip(FlatParamModule):
         attention probabilities)."""
         r, l = tokens.shape
         km = None if attention_mask is None else attention_mask.to(torch.uint8).contiguous()
-        h = ops.gpt2_embed(tokens, self.P("transformer.wte.weight"), self.P("transformer.wpe.weight"))
+        # the step's [seed, step] snapshot: every mask of this forward and of its backward is a function of it
+        snap = ops.dropout_tick(self._drop_state_on(tokens.device)) if self._dropout_on() else None
+        h = ops.gpt2_embed(tokens, self.P("transformer.wte.weight"), self.P("transformer.wpe.weight"),
+                           drop=self._site(snap, 0, self._drop_embd))
         layers = []
         for i in range(self.n_layer):
             q = f"transformer.h.{i}."
             a, mean1, rstd1 = ops.add_layernorm_fwd(h, None, self.P(q + "ln_1.weight"),
                                                     self.P(q + "ln_1.bias"), 1e-5)
             qkv = ops.gemm_nt(a, self._w(q + "attn.c_attn.weight"), self.P(q + "attn.c_attn.bias"))
-            o = ops.attn_causal(qkv, km, r, l, self.n_head)
-            h_mid = ops.gemm_nt(o, self._w(q + "attn.c_proj.weight"), self.P(q + "attn.c_proj.bias"), res=h)
+            o = ops.attn_causal(qkv, km, r, l, self.n_head, drop=self._site(snap, 1 + 3 * i, self._drop_attn))
+            h_mid = self._proj_res(q + "attn.c_proj", o, h, self._site(snap, 2 + 3 * i, self._drop_resid))
             m, mean2, rstd2 = ops.add_layernorm_fwd(h_mid, None, self.P(q + "ln_2.weight"),
                                                     self.P(q + "ln_2.bias"), 1e-5)
             f_pre = ops.gemm_nt(m, self._w(q + "mlp.c_fc.weight"), self.P(q + "mlp.c_fc.bias"))
             f = ops.gelu_new_fwd(f_pre)
-            h_out = ops.gemm_nt(f, self._w(q + "mlp.c_proj.weight"), self.P(q + "mlp.c_proj.bias"), res=h_mid)
+            h_out = self._proj_res(q + "mlp.c_proj", f, h_mid, self._site(snap, 3 + 3 * i, self._drop_resid))
             layers.append((h, a, mean1, rstd1, qkv, o, h_mid, m, mean2, rstd2, f_pre, f))
             h = h_out
         hf, meanf, rstdf = ops.add_layernorm_fwd(h, None, self.P("transformer.ln_f.weight"),
                                                  self.P("transformer.ln_f.bias"), 1e-5)
         logits = ops.gemm_nt(hf, self.P("transformer.wte.weight"))
-        self._saved = (tokens, km, r, l, layers, h, hf, meanf, rstdf)
+        self._saved = (tokens, km, r, l, layers, h, hf, meanf, rstdf, snap)
         return logits.view(r, l, -1)
+
+    @staticmethod
+    def _site(snap, site, params):
+        """The `drop` operand of one dropout site: (snap, site, thr, scale), None when its probability is 0."""
+        return None if params is None else (snap, site) + params
+
+    def _proj_res(self, name, x, res, drop):
+        """res + dropout(x W + b): at a dropout site the GEMM runs without the residual and the mask kernel adds it
+        (the GEMM epilogues and the split-K reduce stay as they are)."""
+        if drop is None:
+            return ops.gemm_nt(x, self._w(name + ".weight"), self.P(name + ".bias"), res=res)
+        return ops.dropout_add(ops.gemm_nt(x, self._w(name + ".weight"), self.P(name + ".bias")), res, drop)
 
     @torch.no_grad()
     def backward(self, dlogits):
         """dlogits [R*L, V] -> .grad of every parameter (overwrite semantics, like the trunk)."""
-        tokens, km, r, l, layers, h_last, hf, meanf, rstdf = self._saved
+        tokens, km, r, l, layers, h_last, hf, meanf, rstdf, snap = self._saved
         self._saved = None
         wte = self.P("transformer.wte.weight")
         dlogits = dlogits.reshape(r * l, -1)
@@ -289,15 +358,19 @@ class GPT2LMHeadModelHip(FlatParamModule):
         for i in reversed(range(self.n_layer)):
             q = f"transformer.h.{i}."
             h_in, a, mean1, rstd1, qkv, o, h_mid, m, mean2, rstd2, f_pre, f = layers[i]
-            df = self._linear_bwd(q + "mlp.c_proj", f, dh, conv1d=True)
+            s_attn, s_proj, s_mlp = (self._site(snap, k + 3 * i, p) for k, p in
+                                     ((1, self._drop_attn), (2, self._drop_resid), (3, self._drop_resid)))
+            df = self._linear_bwd(q + "mlp.c_proj", f, dh if s_mlp is None else ops.dropout_add(dh, None, s_mlp),
+                                  conv1d=True)
             df_pre = ops.gelu_new_bwd(df, f_pre)
             dm = self._linear_bwd(q + "mlp.c_fc", m, df_pre, conv1d=True)
             dmid_ln, _, _, _ = ops.add_layernorm_bwd(dm, h_mid, None, self.P(q + "ln_2.weight"), mean2, rstd2,
                                                      dg_out=self._grad(q + "ln_2.weight"),
                                                      db_out=self._grad(q + "ln_2.bias"))
             d_mid = ops.add_f32(dh, dmid_ln)
-            do = self._linear_bwd(q + "attn.c_proj", o, d_mid, conv1d=True)
-            dqkv = ops.attn_causal_bwd(qkv, km, do, r, l, self.n_head)
+            do = self._linear_bwd(q + "attn.c_proj", o,
+                                  d_mid if s_proj is None else ops.dropout_add(d_mid, None, s_proj), conv1d=True)
+            dqkv = ops.attn_causal_bwd(qkv, km, do, r, l, self.n_head, drop=s_attn)
             da = self._linear_bwd(q + "attn.c_attn", a, dqkv, conv1d=True)
             din_ln, _, _, _ = ops.add_layernorm_bwd(da, h_in, None, self.P(q + "ln_1.weight"), mean1, rstd1,
                                                     dg_out=self._grad(q + "ln_1.weight"),
@@ -306,6 +379,9 @@ class GPT2LMHeadModelHip(FlatParamModule):
             layers[i] = None
         dwpe = self._grad("transformer.wpe.weight")
         dwpe.zero_()
+        s_embd = self._site(snap, 0, self._drop_embd)
+        if s_embd is not None:
+            dh = ops.dropout_add(dh, None, s_embd)
         ops.gpt2_embed_bwd(tokens, dh, dwte, dwpe)  # adds the embedding rows onto the lm_head gradient
         self._drop_copies()  # the optimizer is about to change the parameters
 
@@ -343,7 +419,10 @@ class HuggingFaceGPT2Decoder(nn.Module):
         super().__init__()
         self.dictionary = dictionary
         dims = GPT2_DIMS[args.mdl.gpt2_mdl_name]
-        self.model = GPT2LMHeadModelHip(*dims)
+        # one number for the three probabilities, as hf_gpt2_fseq.py:144-146 intended; absent in the reference's
+        # own config file, hence the default
+        pdrop = float(args.mdl.get("gpt2_dropout", 0.0))
+        self.model = GPT2LMHeadModelHip(*dims, embd_pdrop=pdrop, attn_pdrop=pdrop, resid_pdrop=pdrop)
         if state_dict is not None:
             self.model.load_state_dict(state_dict)
         self.voc_size = len(dictionary)

@@ -1319,22 +1319,72 @@ def layernorm_fwd_packed(x, gamma, beta, eps=1e-5):
     return y
 
 
-def gpt2_embed(tokens, wte, wpe, pos0=0):
+# ---- train-mode dropout from the in-kernel counter generator (csrc/dropout_rng.h) -------------------------------
+# `drop` below is (snap, site, thr, scale): the step's [seed, step] snapshot (dropout_tick), the site number and the
+# pair dropout_params(p) returns.  None = the plain entry point.
+def dropout_params(p):
+    """p -> (thr, scale) of the mask contract; refuses p outside 0 <= p < 1."""
+    thr, scale = C.c_uint32(), C.c_float()
+    _lib.call("vs_dropout_threshold", float(p), C.byref(thr), C.byref(scale))
+    return thr.value, scale.value
+
+
+def dropout_mask_host(seed, step, site, e0, n, thr):
+    """The keep mask of elements e0 .. e0 + n - 1 as a CPU uint8 tensor (host code, no GPU)."""
+    keep = torch.empty(int(n), dtype=torch.uint8)
+    _lib.call("vs_dropout_mask_host", int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), int(site), int(e0), int(n),
+              int(thr), C.c_void_p(keep.data_ptr()))
+    return keep
+
+
+def dropout_tick(state):
+    """state i64 [seed, step] (device) -> a new snapshot of it; the state's step advances by one."""
+    if state.dtype != torch.int64 or state.numel() != 2 or not state.is_contiguous():
+        raise _lib.VsError("dropout_tick: state must be a contiguous int64 [2] tensor")
+    snap = torch.empty_like(state)
+    _lib.call("vs_dropout_tick", _ptr(state), _ptr(snap), _stream())
+    return snap
+
+
+def dropout_add(x, res, drop, out=None):
+    """out = res + m * x (res may be None); element index = the flat index."""
+    x = _f32c(x)
+    res = None if res is None else _f32c(res)
+    if res is not None and res.numel() != x.numel():
+        raise _lib.VsError("dropout_add: x and res differ in size")
+    out = torch.empty_like(x) if out is None else out
+    snap, site, thr, scale = drop
+    _lib.call("vs_dropout_add_f32", _ptr(x), _ptr(res), _ptr(out), x.numel(), _ptr(snap), int(site), int(thr),
+              float(scale), _stream())
+    return out
+
+
+def gpt2_embed(tokens, wte, wpe, pos0=0, drop=None):
     """tokens i64 [R, L] -> f32 [R*L, D] = wte[tok] + wpe[pos0 + l]."""
     tokens = tokens.contiguous()
     r, l = tokens.shape
     if pos0 + l > wpe.shape[0]:
         raise _lib.VsError(f"gpt2_embed: position {pos0 + l} beyond n_positions {wpe.shape[0]}")
     out = torch.empty((r * l, wte.shape[1]), dtype=torch.float32, device=wte.device)
+    if drop is not None:
+        snap, site, thr, scale = drop
+        _lib.call("vs_gpt2_embed_drop", _ptr(tokens), _ptr(wte), _ptr(wpe), _ptr(out), r, l, wte.shape[1],
+                  int(pos0), wte.shape[0], _ptr(snap), int(site), int(thr), float(scale), _stream())
+        return out
     _lib.call("vs_gpt2_embed", _ptr(tokens), _ptr(wte), _ptr(wpe), _ptr(out), r, l, wte.shape[1],
               int(pos0), wte.shape[0], _stream())
     return out
 
 
-def attn_causal(qkv, key_mask, r, l, n_head):
+def attn_causal(qkv, key_mask, r, l, n_head, drop=None):
     """qkv f32 [R*L, 3D]; key_mask uint8 [R, L] or None -> f32 [R*L, D]."""
     d = qkv.shape[1] // 3
     out = torch.empty((r * l, d), dtype=torch.float32, device=qkv.device)
+    if drop is not None:
+        snap, site, thr, scale = drop
+        _lib.call("vs_attn_causal_drop_fwd", _ptr(qkv), _ptr(key_mask), _ptr(out), r, l, n_head, d // n_head,
+                  _ptr(snap), int(site), int(thr), float(scale), _stream())
+        return out
     _lib.call("vs_attn_causal_fwd", _ptr(qkv), _ptr(key_mask), _ptr(out), r, l, n_head, d // n_head,
               _stream())
     return out
@@ -1442,11 +1492,17 @@ def colsum_f32(x, out=None):
     return out
 
 
-def attn_causal_bwd(qkv, key_mask, dout, r, l, n_head):
+def attn_causal_bwd(qkv, key_mask, dout, r, l, n_head, drop=None):
     d = qkv.shape[1] // 3
     dqkv = torch.empty_like(qkv)
     need = _lib.load().vs_attn_causal_bwd_scratch_bytes(r, l, n_head)
     ws = _workspace(need, qkv.device)
+    if drop is not None:
+        snap, site, thr, scale = drop
+        _lib.call("vs_attn_causal_drop_bwd", _ptr(qkv), _ptr(key_mask), _ptr(_f32c(dout)), _ptr(dqkv), _ptr(ws),
+                  C.c_size_t(ws.numel()), r, l, n_head, d // n_head, _ptr(snap), int(site), int(thr), float(scale),
+                  _stream())
+        return dqkv
     _lib.call("vs_attn_causal_bwd", _ptr(qkv), _ptr(key_mask), _ptr(_f32c(dout)), _ptr(dqkv), _ptr(ws),
               C.c_size_t(ws.numel()), r, l, n_head, d // n_head, _stream())
     return dqkv

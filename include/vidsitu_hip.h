@@ -683,6 +683,17 @@ int vs_attn_causal_drop_fwd(const float* qkv, const uint8_t* key_mask, float* ou
 int vs_attn_causal_drop_bwd(const float* qkv, const uint8_t* key_mask, const float* dout, float* dqkv, void* scratch,
                             size_t scratch_bytes, int R, int L, int H, int dh, const int64_t* snap, uint32_t site,
                             uint32_t thr, float scale, void* stream);
+/* vs_attn_pad_fwd / _bwd (the RoBERTa encoder's attention, below) with dropout on the attention probabilities:
+ * out_i = sum_j p_ij m_ij v_j, p the undropped softmax.  The element index is the causal kernels' --
+ * ((r*H + h)*L + i)*Lp4 + j with Lp4 = (L + 3) & ~3 -- not the kernel's 16-wide tile pitch.  Same kernels (one
+ * template, which the plain entry points instantiate without the mask and whose results stay theirs bit for bit), same
+ * grid, LDS size, head widths, L limits and scratch size; nothing is stored between forward and backward; no atomics.
+ * A masked key has weight exactly 0, dropped or not.  The backward's scratch must be 16-byte aligned. */
+int vs_attn_pad_drop_fwd(const float* qkv, const uint8_t* key_mask, float* out, int R, int L, int H, int dh,
+                         const int64_t* snap, uint32_t site, uint32_t thr, float scale, void* stream);
+int vs_attn_pad_drop_bwd(const float* qkv, const uint8_t* key_mask, const float* dout, float* dqkv, void* scratch,
+                         size_t scratch_bytes, int R, int L, int H, int dh, const int64_t* snap, uint32_t site,
+                         uint32_t thr, float scale, void* stream);
 
 /* Device-side beam-search bookkeeping of one step (SeqGenCustom._generate between two decoder
  * calls, seq_gen.py:368-520, and finalize_hypos :579-697), one block per sentence, no host sync:

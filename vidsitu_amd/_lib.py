@@ -208,6 +208,8 @@ SIGNATURES = {
     "vs_gpt2_embed_drop": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _u32, _u32, _f, _p]),
     "vs_attn_causal_drop_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _u32, _u32, _f, _p]),
     "vs_attn_causal_drop_bwd": (_i, [_p, _p, _p, _p, _p, _sz, _i, _i, _i, _i, _p, _u32, _u32, _f, _p]),
+    "vs_attn_pad_drop_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _u32, _u32, _f, _p]),
+    "vs_attn_pad_drop_bwd": (_i, [_p, _p, _p, _p, _p, _sz, _i, _i, _i, _i, _p, _u32, _u32, _f, _p]),
     "vs_attn_pad_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "vs_attn_pad_bwd_scratch_bytes": (_sz, [_i, _i, _i]),
     "vs_attn_pad_bwd": (_i, [_p, _p, _p, _p, _p, _sz, _i, _i, _i, _i, _p]),

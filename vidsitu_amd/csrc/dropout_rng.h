@@ -66,3 +66,10 @@ VS_RNG_HD int vs_dropout_keep(uint64_t seed, uint64_t step, uint32_t site, uint6
   const vs_philox_out o = vs_dropout_block(seed, step, site, e >> 2);
   return o.w[e & 3] >= thr;
 }
+
+// What a kernel with a dropout site takes: the step's snapshot and the site's number, threshold and scale.
+struct DropArgs {
+  const int64_t* snap;  // [seed, step] of this step (vs_dropout_tick)
+  uint32_t site, thr;
+  float scale;
+};

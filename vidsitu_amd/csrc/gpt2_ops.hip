@@ -240,12 +240,6 @@ extern "C" int vs_gemm_nt_f32_ws(const float* x, const float* w, const float* b,
 // ----------------------------------------------------------------------------
 // DROP: the embedding dropout on wte + wpe before the store; element index = the flat index in [R*L, D], so the four
 // floats of a thread are one Philox block.
-struct DropArgs {
-  const int64_t* snap;  // [seed, step] of this step (vs_dropout_tick)
-  uint32_t site, thr;
-  float scale;
-};
-
 template <bool DROP>
 __global__ void gpt2_embed_kernel(const int64_t* tok, const float* wte, const float* wpe, float* out,
                                   int rows, int L, int D, int pos0, int V, DropArgs dr) {

@@ -5,6 +5,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "dropout_rng.h"
 
 // ----------------------------------------------------------------------------
 // Self-attention over a fused qkv buffer [R, L, 3D]:
@@ -50,10 +51,23 @@ __device__ __forceinline__ bool ap_any_key_valid(const uint8_t* kmask, int r, in
   return __syncthreads_or(any) != 0;
 }
 
-template <int DH>
+// DROP (train-mode dropout on the probabilities, out_i = sum_j p_ij m_ij v_j with the row sum taken before the mask):
+// element index of (r, h, i, j) = ((r * H + h) * L + i) * Lp4 + j with Lp4 = (L + 3) & ~3 -- the causal kernel's
+// convention, not this kernel's 16-wide Lp -- so four consecutive keys of a query are one Philox block.  The softmax
+// passes give a row's four lanes the columns c0, c0 + 4, ...; the mask passes give them whole blocks (columns 4b ..
+// 4b + 3 for b = c0, c0 + 4, ...): one draw per four keys, and the plain kernel's summation order stays as it is.
+// -> the four multipliers (0 or scale) of block b of the row whose first block is rowblk
+__device__ __forceinline__ float4 ap_mask4(const DropArgs& dr, uint64_t seed, uint64_t step, uint64_t rowblk, int b) {
+  const vs_philox_out w = vs_dropout_block(seed, step, dr.site, rowblk + (uint64_t)b);
+  return make_float4(w.w[0] >= dr.thr ? dr.scale : 0.f, w.w[1] >= dr.thr ? dr.scale : 0.f,
+                     w.w[2] >= dr.thr ? dr.scale : 0.f, w.w[3] >= dr.thr ? dr.scale : 0.f);
+}
+
+template <int DH, bool DROP>
 __global__ __launch_bounds__(256) void attn_pad_fwd_kernel(const float* __restrict__ qkv,
                                                            const uint8_t* __restrict__ kmask,
-                                                           float* __restrict__ out, int L, int Lp, int H) {
+                                                           float* __restrict__ out, int L, int Lp, int H,
+                                                           DropArgs dr) {
   extern __shared__ float sm[];
   constexpr int LD = DH + 4, KS = DH / 4, CT = DH / 16;
   const int D = H * DH, LS = Lp + 4;
@@ -110,6 +124,20 @@ __global__ __launch_bounds__(256) void attn_pad_fwd_kernel(const float* __restri
     sum += __shfl_xor(sum, 1, 64);
     sum += __shfl_xor(sum, 2, 64);
     inv = 1.0f / sum;
+    if (DROP) {  // e_ij *= m_ij; the row sum above is the undropped one
+      __builtin_amdgcn_wave_barrier();  // the row's other three lanes wrote what this lane reads
+      const int i = i0 + (lane >> 2);
+      if (i < L) {
+        const uint64_t seed = (uint64_t)dr.snap[0], step = (uint64_t)dr.snap[1];
+        const uint64_t rowblk = ((uint64_t)blockIdx.x * L + i) * (uint64_t)((L + 3) >> 2);
+        for (int b = c0; b * 4 < L; b += 4) {  // columns L .. 4b + 3 of the last block hold 0 and stay 0
+          const float4 m = ap_mask4(dr, seed, step, rowblk, b);
+          float4 e = *(float4*)(row + b * 4);
+          e.x *= m.x; e.y *= m.y; e.z *= m.z; e.w *= m.w;
+          *(float4*)(row + b * 4) = e;
+        }
+      }
+    }
   }
   __syncthreads();
   if (active) {
@@ -154,21 +182,22 @@ static bool ap_lds_attr(const void* kernel) {
   return false;
 }
 
-template <int DH>
+template <int DH, bool DROP>
 static int ap_fwd_launch(const float* qkv, const uint8_t* km, float* out, int R, int L, int H, size_t smem,
-                         hipStream_t st) {
+                         DropArgs dr, hipStream_t st) {
   static bool attr = false;
   if (!attr) {
-    if (!ap_lds_attr((const void*)attn_pad_fwd_kernel<DH>)) return VS_ERR_LAUNCH;
+    if (!ap_lds_attr((const void*)attn_pad_fwd_kernel<DH, DROP>)) return VS_ERR_LAUNCH;
     attr = true;
   }
-  hipLaunchKernelGGL(attn_pad_fwd_kernel<DH>, dim3(R * H, (L + AP_QT - 1) / AP_QT), dim3(256), smem, st, qkv, km,
-                     out, L, ap_lp(L), H);
+  hipLaunchKernelGGL((attn_pad_fwd_kernel<DH, DROP>), dim3(R * H, (L + AP_QT - 1) / AP_QT), dim3(256), smem, st, qkv,
+                     km, out, L, ap_lp(L), H, dr);
   return VS_OK;
 }
 
-extern "C" int vs_attn_pad_fwd(const float* qkv, const uint8_t* key_mask, float* out, int R, int L, int H, int dh,
-                               void* stream) {
+template <bool DROP>
+static int ap_fwd(const float* qkv, const uint8_t* key_mask, float* out, int R, int L, int H, int dh, DropArgs dr,
+                  void* stream) {
   VS_CHECK_ARG(qkv && out && R > 0 && L > 0 && H > 0, "bad args");
   VS_CHECK_ARG(ap_dh_ok(dh), "head width must be 16, 32, 64 or 128");
   VS_CHECK_ARG((long long)R * H <= 0x7fffffffLL, "too many (sequence, head) pairs");
@@ -177,14 +206,26 @@ extern "C" int vs_attn_pad_fwd(const float* qkv, const uint8_t* key_mask, float*
   hipStream_t st = (hipStream_t)stream;
   int rc;
   switch (dh) {
-    case 16: rc = ap_fwd_launch<16>(qkv, key_mask, out, R, L, H, smem, st); break;
-    case 32: rc = ap_fwd_launch<32>(qkv, key_mask, out, R, L, H, smem, st); break;
-    case 64: rc = ap_fwd_launch<64>(qkv, key_mask, out, R, L, H, smem, st); break;
-    default: rc = ap_fwd_launch<128>(qkv, key_mask, out, R, L, H, smem, st); break;
+    case 16: rc = ap_fwd_launch<16, DROP>(qkv, key_mask, out, R, L, H, smem, dr, st); break;
+    case 32: rc = ap_fwd_launch<32, DROP>(qkv, key_mask, out, R, L, H, smem, dr, st); break;
+    case 64: rc = ap_fwd_launch<64, DROP>(qkv, key_mask, out, R, L, H, smem, dr, st); break;
+    default: rc = ap_fwd_launch<128, DROP>(qkv, key_mask, out, R, L, H, smem, dr, st); break;
   }
   if (rc != VS_OK) return rc;
   VS_CHECK_LAUNCH();
   return VS_OK;
+}
+
+extern "C" int vs_attn_pad_fwd(const float* qkv, const uint8_t* key_mask, float* out, int R, int L, int H, int dh,
+                               void* stream) {
+  return ap_fwd<false>(qkv, key_mask, out, R, L, H, dh, DropArgs{}, stream);
+}
+
+extern "C" int vs_attn_pad_drop_fwd(const float* qkv, const uint8_t* key_mask, float* out, int R, int L, int H,
+                                    int dh, const int64_t* snap, uint32_t site, uint32_t thr, float scale,
+                                    void* stream) {
+  VS_CHECK_ARG(snap, "bad args");
+  return ap_fwd<true>(qkv, key_mask, out, R, L, H, dh, DropArgs{snap, site, thr, scale}, stream);
 }
 
 // ----------------------------------------------------------------------------
@@ -196,13 +237,16 @@ extern "C" int vs_attn_pad_fwd(const float* qkv, const uint8_t* key_mask, float*
 //   operand read straight from the scratch: dV = P^T dO, dK = scale * dS^T Q.
 // Every output element has one owner and a fixed summation order (k-ordered fma chains of the instruction): no
 // atomics, two runs agree bit for bit.
+// DROP (out = (p o m) v, the mask regenerated from the step's snapshot as in the forward): dP = m o (dO V^T), D and dS
+// as above from the undropped p, and the scratch's p rows hold p o m -- launch A writes them from the mask pass, where
+// a lane has both -- so that launch B (dV = (p o m)^T dO) is the plain one.
 // ----------------------------------------------------------------------------
-template <int DH>
+template <int DH, bool DROP>
 __global__ __launch_bounds__(256) void attn_pad_bwd_q_kernel(const float* __restrict__ qkv,
                                                              const uint8_t* __restrict__ kmask,
                                                              const float* __restrict__ dout,
                                                              float* __restrict__ dqkv, float* __restrict__ scratch,
-                                                             int L, int Lp, int H) {
+                                                             int L, int Lp, int H, DropArgs dr) {
   extern __shared__ float sm[];
   constexpr int LD = DH + 4, KS = DH / 4, CT = DH / 16;
   const int D = H * DH, LS = Lp + 4;
@@ -272,17 +316,54 @@ __global__ __launch_bounds__(256) void attn_pad_bwd_q_kernel(const float* __rest
     sum += __shfl_xor(sum, 2, 64);
     const float inv = 1.0f / sum;
     float dsum = 0.f;
-    for (int c = c0; c < L; c += 4) {
-      const float p = row[c] * inv;
-      row[c] = p;
-      dsum += p * drow[c];
-    }
-    dsum += __shfl_xor(dsum, 1, 64);
-    dsum += __shfl_xor(dsum, 2, 64);
-    for (int c = c0; c < L; c += 4) drow[c] = row[c] * (drow[c] - dsum);
-    for (int c = L + c0; c < Lp; c += 4) {
-      row[c] = 0.f;
-      drow[c] = 0.f;
+    if (DROP) {
+      __builtin_amdgcn_wave_barrier();  // the row's other three lanes wrote what this lane reads
+      const int i = i0 + (lane >> 2);
+      const bool live = i < L;  // a row past L owns no scratch row and no output; its strip is never read for one
+      const uint64_t seed = (uint64_t)dr.snap[0], step = (uint64_t)dr.snap[1];
+      const uint64_t rowblk = ((uint64_t)blockIdx.x * L + (live ? i : 0)) * (uint64_t)((L + 3) >> 2);
+      float4* pg4 = (float4*)(Pg + (long long)(live ? i : 0) * Lp);
+      if (live)
+        for (int b = c0; b < Lp / 4; b += 4) {  // blocks, not strided columns; the blocks past L are zero
+          const int j = b * 4;
+          float4 p = make_float4(0.f, 0.f, 0.f, 0.f), g = p, pm = p;
+          if (j < L) {
+            const float4 m = ap_mask4(dr, seed, step, rowblk, b);
+            const float4 e = *(const float4*)(row + j), d = *(const float4*)(drow + j);
+            p.x = e.x * inv;
+            g.x = m.x * d.x;
+            pm.x = p.x * m.x;
+            if (j + 1 < L) { p.y = e.y * inv; g.y = m.y * d.y; pm.y = p.y * m.y; }
+            if (j + 2 < L) { p.z = e.z * inv; g.z = m.z * d.z; pm.z = p.z * m.z; }
+            if (j + 3 < L) { p.w = e.w * inv; g.w = m.w * d.w; pm.w = p.w * m.w; }
+            dsum += (p.x * g.x + p.y * g.y) + (p.z * g.z + p.w * g.w);
+          }
+          *(float4*)(row + j) = p;
+          *(float4*)(drow + j) = g;
+          pg4[b] = pm;
+        }
+      dsum += __shfl_xor(dsum, 1, 64);
+      dsum += __shfl_xor(dsum, 2, 64);
+      if (live)
+        for (int b = c0; b * 4 < L; b += 4) {  // the same lane's own blocks: dS = p (dP - D); p = 0 past L
+          const float4 p = *(const float4*)(row + b * 4);
+          float4 g = *(const float4*)(drow + b * 4);
+          g.x = p.x * (g.x - dsum); g.y = p.y * (g.y - dsum); g.z = p.z * (g.z - dsum); g.w = p.w * (g.w - dsum);
+          *(float4*)(drow + b * 4) = g;
+        }
+    } else {
+      for (int c = c0; c < L; c += 4) {
+        const float p = row[c] * inv;
+        row[c] = p;
+        dsum += p * drow[c];
+      }
+      dsum += __shfl_xor(dsum, 1, 64);
+      dsum += __shfl_xor(dsum, 2, 64);
+      for (int c = c0; c < L; c += 4) drow[c] = row[c] * (drow[c] - dsum);
+      for (int c = L + c0; c < Lp; c += 4) {
+        row[c] = 0.f;
+        drow[c] = 0.f;
+      }
     }
   }
   __syncthreads();
@@ -291,7 +372,7 @@ __global__ __launch_bounds__(256) void attn_pad_bwd_q_kernel(const float* __rest
       const int i = i0 + rw;
       if (i >= L) break;
       for (int c = lane; c < Lp; c += 64) {
-        Pg[(long long)i * Lp + c] = Pw[rw * LS + c];
+        if (!DROP) Pg[(long long)i * Lp + c] = Pw[rw * LS + c];  // DROP: p o m went out from the mask pass
         Sg[(long long)i * Lp + c] = Dw[rw * LS + c];
       }
     }
@@ -377,26 +458,28 @@ extern "C" size_t vs_attn_pad_bwd_scratch_bytes(int R, int L, int H) {
   return (size_t)R * H * 2 * L * ap_lp(L) * sizeof(float);
 }
 
-template <int DH>
+template <int DH, bool DROP>
 static int ap_bwd_launch(const float* qkv, const uint8_t* km, const float* dout, float* dqkv, float* scratch,
-                          int R, int L, int H, hipStream_t st) {
+                          int R, int L, int H, DropArgs dr, hipStream_t st) {
   static bool attr = false;
   if (!attr) {
-    if (!ap_lds_attr((const void*)attn_pad_bwd_q_kernel<DH>) || !ap_lds_attr((const void*)attn_pad_bwd_kv_kernel<DH>))
+    if (!ap_lds_attr((const void*)attn_pad_bwd_q_kernel<DH, DROP>) ||
+        !ap_lds_attr((const void*)attn_pad_bwd_kv_kernel<DH>))
       return VS_ERR_LAUNCH;
     attr = true;
   }
   const int Lp = ap_lp(L);
   const dim3 grid(R * H, (L + AP_QT - 1) / AP_QT);
-  hipLaunchKernelGGL(attn_pad_bwd_q_kernel<DH>, grid, dim3(256), ap_bwd_smem(L, DH), st, qkv, km, dout, dqkv,
-                     scratch, L, Lp, H);
+  hipLaunchKernelGGL((attn_pad_bwd_q_kernel<DH, DROP>), grid, dim3(256), ap_bwd_smem(L, DH), st, qkv, km, dout, dqkv,
+                     scratch, L, Lp, H, dr);
   hipLaunchKernelGGL(attn_pad_bwd_kv_kernel<DH>, grid, dim3(256), (size_t)2 * Lp * (DH + 4) * sizeof(float), st,
                      qkv, dout, dqkv, (const float*)scratch, L, Lp, H);
   return VS_OK;
 }
 
-extern "C" int vs_attn_pad_bwd(const float* qkv, const uint8_t* key_mask, const float* dout, float* dqkv,
-                               void* scratch, size_t scratch_bytes, int R, int L, int H, int dh, void* stream) {
+template <bool DROP>
+static int ap_bwd(const float* qkv, const uint8_t* key_mask, const float* dout, float* dqkv, void* scratch,
+                  size_t scratch_bytes, int R, int L, int H, int dh, DropArgs dr, void* stream) {
   VS_CHECK_ARG(qkv && dout && dqkv && scratch && R > 0 && L > 0 && H > 0, "bad args");
   VS_CHECK_ARG(ap_dh_ok(dh), "head width must be 16, 32, 64 or 128");
   VS_CHECK_ARG((long long)R * H <= 0x7fffffffLL, "too many (sequence, head) pairs");
@@ -405,14 +488,28 @@ extern "C" int vs_attn_pad_bwd(const float* qkv, const uint8_t* key_mask, const 
   hipStream_t st = (hipStream_t)stream;
   int rc;
   switch (dh) {
-    case 16: rc = ap_bwd_launch<16>(qkv, key_mask, dout, dqkv, (float*)scratch, R, L, H, st); break;
-    case 32: rc = ap_bwd_launch<32>(qkv, key_mask, dout, dqkv, (float*)scratch, R, L, H, st); break;
-    case 64: rc = ap_bwd_launch<64>(qkv, key_mask, dout, dqkv, (float*)scratch, R, L, H, st); break;
-    default: rc = ap_bwd_launch<128>(qkv, key_mask, dout, dqkv, (float*)scratch, R, L, H, st); break;
+    case 16: rc = ap_bwd_launch<16, DROP>(qkv, key_mask, dout, dqkv, (float*)scratch, R, L, H, dr, st); break;
+    case 32: rc = ap_bwd_launch<32, DROP>(qkv, key_mask, dout, dqkv, (float*)scratch, R, L, H, dr, st); break;
+    case 64: rc = ap_bwd_launch<64, DROP>(qkv, key_mask, dout, dqkv, (float*)scratch, R, L, H, dr, st); break;
+    default: rc = ap_bwd_launch<128, DROP>(qkv, key_mask, dout, dqkv, (float*)scratch, R, L, H, dr, st); break;
   }
   if (rc != VS_OK) return rc;
   VS_CHECK_LAUNCH();
   return VS_OK;
+}
+
+extern "C" int vs_attn_pad_bwd(const float* qkv, const uint8_t* key_mask, const float* dout, float* dqkv,
+                               void* scratch, size_t scratch_bytes, int R, int L, int H, int dh, void* stream) {
+  return ap_bwd<false>(qkv, key_mask, dout, dqkv, scratch, scratch_bytes, R, L, H, dh, DropArgs{}, stream);
+}
+
+extern "C" int vs_attn_pad_drop_bwd(const float* qkv, const uint8_t* key_mask, const float* dout, float* dqkv,
+                                    void* scratch, size_t scratch_bytes, int R, int L, int H, int dh,
+                                    const int64_t* snap, uint32_t site, uint32_t thr, float scale, void* stream) {
+  VS_CHECK_ARG(snap, "bad args");
+  VS_CHECK_ARG(((uintptr_t)scratch & 15) == 0, "scratch must be 16-byte aligned");
+  return ap_bwd<true>(qkv, key_mask, dout, dqkv, scratch, scratch_bytes, R, L, H, dh, DropArgs{snap, site, thr, scale},
+                      stream);
 }
 
 // ----------------------------------------------------------------------------

@@ -6,6 +6,12 @@ a graph capture and die when the parameters move or change, saves activations in
 in a hand-written `backward`, and hides behind ONE autograd node fed by a dummy `tick` tensor.  `FlatParamModule`
 owns all of that; a model provides its list of names / shapes / initialisers, `forward_train`, `backward`, and where
 its checkpoints need them the hooks `_extra_state` / `_tolerated_on_load`, `_CACHES` and `_CAPTURE_MSG`.
+
+A model with train-mode dropout (the counter generator of csrc/dropout_rng.h) also keeps its `[seed, step]` state here:
+`_drop_state_on` creates it at the first train-mode forward, `dropout_state` / `set_dropout_state` read and continue
+it, `.to()` moves it.  It is no parameter and no buffer (absent from the state dict); a model whose probabilities are
+all 0 never calls `_drop_state_on` and allocates nothing.  Hooks: `_drop_anchor` (the parameter whose device the state
+follows) and `_DROP_CAPTURE_MSG`.
 """
 import torch
 from torch import nn
@@ -16,6 +22,8 @@ from . import ops
 class FlatParamModule(nn.Module):
     _CACHES = ()  # names of the dicts of derived weight copies; `_drop_copies` empties them
     _CAPTURE_MSG = "derived weight copies must exist before a graph capture (run one eager step first)"
+    _DROP_CAPTURE_MSG = "the dropout state must exist before a graph capture (run one eager step first)"
+    _drop_state = None  # i64 [seed, step] on the device: not a parameter, not in the state dict
 
     def _register_flat(self, params):
         """params: ordered {upstream name: tensor | Parameter}; registration order = `named_parameters()` order."""
@@ -86,7 +94,49 @@ class FlatParamModule(nn.Module):
 
     def _apply(self, fn, *args, **kwargs):
         self._drop_copies()  # device / dtype moves replace the parameters' storage
-        return super()._apply(fn, *args, **kwargs)
+        out = super()._apply(fn, *args, **kwargs)
+        if self._drop_state is not None:  # the state moves with .to(); it stays int64 under a dtype cast
+            self._drop_state = self._drop_state.to(self._drop_anchor().device)
+        return out
+
+    # ---- dropout state -------------------------------------------------------------------------------
+    def _drop_anchor(self):
+        """The parameter whose device the dropout state follows."""
+        return self.P(self._names[0])
+
+    @staticmethod
+    def _site(snap, site, params):
+        """The `drop` operand of one dropout site: (snap, site, thr, scale), None when its probability is 0."""
+        return None if params is None else (snap, site) + params
+
+    def _drop_state_on(self, device):
+        """The persistent [seed, step] buffer on `device`; the seed is drawn from torch's default CPU generator at the
+        first train-mode forward (so `torch.manual_seed` governs it)."""
+        st = self._drop_state
+        if st is None or st.device != device:
+            if torch.cuda.is_current_stream_capturing():
+                raise ops._lib.VsError(self._DROP_CAPTURE_MSG)
+            if st is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64))
+                st = torch.tensor([seed, 0], dtype=torch.int64)
+            st = self._drop_state = st.to(device)
+        return st
+
+    def dropout_state(self):
+        """(seed, step) of the next train-mode forward, or None before the first one."""
+        if self._drop_state is None:
+            return None
+        seed, step = self._drop_state.tolist()
+        return seed, step
+
+    def set_dropout_state(self, state):
+        """Continue from `(seed, step)` (what `dropout_state()` returned).  Written in place when the buffer exists:
+        captured training steps keep reading the same memory."""
+        new = torch.tensor([int(state[0]), int(state[1])], dtype=torch.int64)
+        if self._drop_state is None:
+            self._drop_state = new.to(self._drop_anchor().device)
+        else:
+            self._drop_state.copy_(new)
 
     # ---- backward of a dense layer ---------------------------------------------------------------------
     def _linear_bwd(self, name, x, dy, bias=True, need_dx=True, conv1d=False):

@@ -86,7 +86,6 @@ class GPT2LMHeadModelHip(FlatParamModule):
         # (thr, scale) per probability, None at p = 0 (that site then runs today's launches); refuses p outside [0, 1)
         self._drop_embd, self._drop_attn, self._drop_resid = (
             ops.dropout_params(p) if p != 0.0 else None for p in (embd_pdrop, attn_pdrop, resid_pdrop))
-        self._drop_state = None  # i64 [seed, step] on the device: not a parameter, not in the state dict
         self.config = type("Cfg", (), {"n_positions": n_positions, "n_embd": d_model,
                                        "n_layer": n_layer, "n_head": n_head,
                                        "vocab_size": vocab_size})()
@@ -152,40 +151,8 @@ class GPT2LMHeadModelHip(FlatParamModule):
     def _dropout_on(self):
         return not (self._drop_embd is None and self._drop_attn is None and self._drop_resid is None)
 
-    def _drop_state_on(self, device):
-        """The persistent [seed, step] buffer on `device`; the seed is drawn from torch's default CPU generator at the
-        first train-mode forward (so `torch.manual_seed` governs it)."""
-        st = self._drop_state
-        if st is None or st.device != device:
-            if torch.cuda.is_current_stream_capturing():
-                raise ops._lib.VsError(self._DROP_CAPTURE_MSG)
-            if st is None:
-                seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64))
-                st = torch.tensor([seed, 0], dtype=torch.int64)
-            st = self._drop_state = st.to(device)
-        return st
-
-    def dropout_state(self):
-        """(seed, step) of the next train-mode forward, or None before the first one."""
-        if self._drop_state is None:
-            return None
-        seed, step = self._drop_state.tolist()
-        return seed, step
-
-    def set_dropout_state(self, state):
-        """Continue from `(seed, step)` (what `dropout_state()` returned).  Written in place when the buffer exists:
-        captured training steps keep reading the same memory."""
-        new = torch.tensor([int(state[0]), int(state[1])], dtype=torch.int64)
-        if self._drop_state is None:
-            self._drop_state = new.to(self.P("transformer.wte.weight").device)
-        else:
-            self._drop_state.copy_(new)
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        if self._drop_state is not None:  # the state moves with .to(); it stays int64 under a dtype cast
-            self._drop_state = self._drop_state.to(self.P("transformer.wte.weight").device)
-        return out
+    def _drop_anchor(self):
+        return self.P("transformer.wte.weight")
 
     # ---- compute ---------------------------------------------------------------------------
     def _block(self, i, h, attn_fn):
@@ -328,11 +295,6 @@ class GPT2LMHeadModelHip(FlatParamModule):
         logits = ops.gemm_nt(hf, self.P("transformer.wte.weight"))
         self._saved = (tokens, km, r, l, layers, h, hf, meanf, rstdf, snap)
         return logits.view(r, l, -1)
-
-    @staticmethod
-    def _site(snap, site, params):
-        """The `drop` operand of one dropout site: (snap, site, thr, scale), None when its probability is 0."""
-        return None if params is None else (snap, site) + params
 
     def _proj_res(self, name, x, res, drop):
         """res + dropout(x W + b): at a dropout site the GEMM runs without the residual and the mask kernel adds it

@@ -11,7 +11,16 @@ Semantics kept from the pinned release: additive key mask `(1 - attention_mask) 
 ids (`create_position_ids_from_input_ids`: padding tokens sit at `padding_idx`, the others count from `padding_idx + 1`),
 the single token-type row, post-LN residual blocks, erf GELU, LayerNorm eps 1e-5 (the checkpoints' value), pooler
 `tanh(dense(h[:, 0]))`, classification head `out_proj(tanh(dense(h[:, 0])))`.
-Stated difference: no dropout anywhere (as in the GPT-2 decoder of this package).
+
+Dropout: `from_pretrained` gives the reference huggingface's defaults (`hidden_dropout_prob =
+attention_probs_dropout_prob = 0.1`); here both are constructor arguments, 0 by default (`mdl.rob_dropout` sets them).
+Above 0 the train-mode pass applies the masks of the pinned release's dropout sites from the counter generator of
+csrc/dropout_rng.h inside the kernels; nothing is stored, the backward regenerates them from the step's `[seed, step]`
+snapshot, which travels with the saved activations.  Site numbers (n layers): 0 the embeddings after their LayerNorm;
+layer i: 1 + 3i the attention probabilities, 2 + 3i `attention.output.dense` before its LayerNorm, 3 + 3i
+`output.dense` before its LayerNorm; classification head: 1 + 3n on `h[:, 0]` before `classifier.dense`, 2 + 3n after
+the tanh before `out_proj`; the pooler has none.  `forward()` and `roberta_apply` outside training never apply dropout
+and never advance the state; at every probability 0 the model issues the launches it issued without the arguments.
 
 Training: `forward_train` keeps the activations, `backward` is a manual HIP backward behind ONE autograd node
 (`roberta_apply` -> `flat_module.FlatTrainFn`); parameter gradients are written with overwrite semantics.  Flat
@@ -38,12 +47,18 @@ class _RobertaHip(FlatParamModule):
     PREFIX = ""
     _CACHES = ("_qkv",)  # layer -> ([3D][D] weight, [3D] bias, [D][3D] transposed weight): one GEMM for q, k and v
     _CAPTURE_MSG = "RoBERTa's fused q/k/v weights must exist before a graph capture (run one eager step first)"
+    _DROP_CAPTURE_MSG = "the RoBERTa dropout state must exist before a graph capture (run one eager step first)"
 
     def __init__(self, n_layer, d_model, n_head, n_positions, vocab_size, d_ffn, pad_token_id=1, layer_norm_eps=1e-5,
-                 add_pooling_layer=True, num_labels=0):
+                 add_pooling_layer=True, num_labels=0, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0):
         super().__init__()
         if d_model % n_head:
             raise ValueError("d_model must be a multiple of n_head")
+        self.hidden_dropout_prob = float(hidden_dropout_prob)
+        self.attention_probs_dropout_prob = float(attention_probs_dropout_prob)
+        # (thr, scale) per probability, None at p = 0 (that site then runs today's launches); refuses p outside [0, 1)
+        self._drop_hid, self._drop_att = (ops.dropout_params(p) if p != 0.0 else None
+                                          for p in (hidden_dropout_prob, attention_probs_dropout_prob))
         self.n_layer, self.d_model, self.n_head, self.n_positions = n_layer, d_model, n_head, n_positions
         self.d_ffn, self.pad, self.eps = d_ffn, pad_token_id, layer_norm_eps
         self.has_pooler, self.num_labels = bool(add_pooling_layer), int(num_labels)
@@ -125,33 +140,61 @@ class _RobertaHip(FlatParamModule):
     def _dense(self, name, x):
         return ops.gemm_nt(x, self.E(name + ".weight"), self.E(name + ".bias"))
 
-    def _encode(self, tokens, attention_mask, keep):
-        """-> (last hidden state [R*L, D], saved activations | None)."""
+    def _tick(self, tokens, keep):
+        """The [seed, step] snapshot of a train-mode pass with dropout (one tick); None otherwise."""
+        if not keep or (self._drop_hid is None and self._drop_att is None):
+            return None
+        return ops.dropout_tick(self._drop_state_on(tokens.device))
+
+    def _ln_site(self, b, res, name, drop):
+        """LayerNorm(res + dropout(b)) -> (b | the sum, y, mean, rstd).  At a dropout site the mask kernel forms
+        s = res + m o b and the LayerNorm runs on s alone; s is what the backward keeps in b's place (a kernel pair that
+        draws the mask inside the LayerNorm passes was built and measured slower: DESIGN.md, "RoBERTa dropout")."""
+        g, bt = self.E(name + ".weight"), self.E(name + ".bias")
+        if drop is None:
+            return (b,) + ops.add_layernorm_fwd(b, res, g, bt, self.eps)
+        s = ops.dropout_add(b, res, drop)
+        return (s,) + ops.add_layernorm_fwd(s, None, g, bt, self.eps)
+
+    def _ln_site_bwd(self, dy, b, res, name, mean, rstd, drop):
+        """-> (d_res, d_b) of `_ln_site` (b: what it returned first); the LayerNorm's parameter gradients are written."""
+        dg, db = self._grad(name + ".weight"), self._grad(name + ".bias")
+        if drop is None:
+            ds = ops.add_layernorm_bwd(dy, b, res, self.P(name + ".weight"), mean, rstd, dg_out=dg, db_out=db)[0]
+            return ds, ds
+        ds = ops.add_layernorm_bwd(dy, b, None, self.P(name + ".weight"), mean, rstd, dg_out=dg, db_out=db)[0]
+        return ds, ops.dropout_add(ds, None, drop)
+
+    def _encode(self, tokens, attention_mask, keep, snap=None):
+        """-> (last hidden state [R*L, D], saved activations | None).  snap: the step's dropout snapshot or None."""
         km = self._check(tokens, attention_mask)
+        hid = None if snap is None else self._drop_hid
+        att = None if snap is None else self._drop_att
         r, l = tokens.shape
         e, pos_ids = ops.roberta_embed(tokens, self.E("embeddings.word_embeddings.weight"),
                                        self.E("embeddings.position_embeddings.weight"),
                                        self.E("embeddings.token_type_embeddings.weight"), self.pad)
         h, mean0, rstd0 = ops.add_layernorm_fwd(e, None, self.E("embeddings.LayerNorm.weight"),
                                                 self.E("embeddings.LayerNorm.bias"), self.eps)
+        if hid is not None:
+            h = ops.dropout_add(h, None, self._site(snap, 0, hid))
         layers = []
         for i in range(self.n_layer):
             q = f"encoder.layer.{i}."
             w, b, _ = self._fused_qkv(i)
             qkv = ops.gemm_nt(h, w, b)
-            ctx = ops.attn_pad(qkv, km, r, l, self.n_head)
+            ctx = ops.attn_pad(qkv, km, r, l, self.n_head, drop=self._site(snap, 1 + 3 * i, att))
             ao = self._dense(q + "attention.output.dense", ctx)
-            h1, mean1, rstd1 = ops.add_layernorm_fwd(ao, h, self.E(q + "attention.output.LayerNorm.weight"),
-                                                     self.E(q + "attention.output.LayerNorm.bias"), self.eps)
+            ao, h1, mean1, rstd1 = self._ln_site(ao, h, q + "attention.output.LayerNorm",
+                                                 self._site(snap, 2 + 3 * i, hid))
             f_pre = self._dense(q + "intermediate.dense", h1)
             f = ops.gelu_erf_fwd(f_pre)
             fo = self._dense(q + "output.dense", f)
-            h2, mean2, rstd2 = ops.add_layernorm_fwd(fo, h1, self.E(q + "output.LayerNorm.weight"),
-                                                     self.E(q + "output.LayerNorm.bias"), self.eps)
+            fo, h2, mean2, rstd2 = self._ln_site(fo, h1, q + "output.LayerNorm", self._site(snap, 3 + 3 * i, hid))
             if keep:
                 layers.append((h, qkv, ctx, ao, mean1, rstd1, h1, f_pre, f, fo, mean2, rstd2))
             h = h2
-        saved = (tokens, pos_ids, km, r, l, e, mean0, rstd0, layers) if keep else None
+        saved = (tokens, pos_ids, km, r, l, e, mean0, rstd0, layers, snap) if keep else None
         return h, saved
 
     def _first_token(self, h, r, l):
@@ -159,22 +202,22 @@ class _RobertaHip(FlatParamModule):
 
     def _encode_bwd(self, saved, dh):
         """dh [R*L, D]: gradient of the last hidden state -> every encoder / embedding parameter's .grad."""
-        tokens, pos_ids, km, r, l, e, mean0, rstd0, layers = saved
+        tokens, pos_ids, km, r, l, e, mean0, rstd0, layers, snap = saved
         d, pre = self.d_model, self.PREFIX  # parameters by their full names from here on
+        hid = None if snap is None else self._drop_hid
+        att = None if snap is None else self._drop_att
         for i in reversed(range(self.n_layer)):
             q = f"{pre}encoder.layer.{i}."
             h_in, qkv, ctx, ao, mean1, rstd1, h1, f_pre, f, fo, mean2, rstd2 = layers[i]
-            ds2 = ops.add_layernorm_bwd(dh, fo, h1, self.P(q + "output.LayerNorm.weight"), mean2, rstd2,
-                                        dg_out=self._grad(q + "output.LayerNorm.weight"),
-                                        db_out=self._grad(q + "output.LayerNorm.bias"))[0]
-            df = self._linear_bwd(q + "output.dense", f, ds2)
+            ds2, dfo = self._ln_site_bwd(dh, fo, h1, q + "output.LayerNorm", mean2, rstd2,
+                                         self._site(snap, 3 + 3 * i, hid))
+            df = self._linear_bwd(q + "output.dense", f, dfo)
             df_pre = ops.gelu_erf_bwd(df, f_pre)
             dh1 = ops.add_f32(self._linear_bwd(q + "intermediate.dense", h1, df_pre), ds2)
-            ds1 = ops.add_layernorm_bwd(dh1, ao, h_in, self.P(q + "attention.output.LayerNorm.weight"), mean1, rstd1,
-                                        dg_out=self._grad(q + "attention.output.LayerNorm.weight"),
-                                        db_out=self._grad(q + "attention.output.LayerNorm.bias"))[0]
-            dctx = self._linear_bwd(q + "attention.output.dense", ctx, ds1)
-            dqkv = ops.attn_pad_bwd(qkv, km, dctx, r, l, self.n_head)
+            ds1, dao = self._ln_site_bwd(dh1, ao, h_in, q + "attention.output.LayerNorm", mean1, rstd1,
+                                         self._site(snap, 2 + 3 * i, hid))
+            dctx = self._linear_bwd(q + "attention.output.dense", ctx, dao)
+            dqkv = ops.attn_pad_bwd(qkv, km, dctx, r, l, self.n_head, drop=self._site(snap, 1 + 3 * i, att))
             # the fused projection: weight gradients straight into the three separate parameters
             _, _, wt = self._fused_qkv(i)
             dqkv_t, h_t = ops.transpose_f32(dqkv), ops.transpose_f32(h_in)
@@ -184,6 +227,8 @@ class _RobertaHip(FlatParamModule):
                 self._grad(q + "attention.self." + nm + ".bias").copy_(db[s * d:(s + 1) * d])
             dh = ops.add_f32(ops.gemm_nt(dqkv, wt), ds1)
             layers[i] = None
+        if hid is not None:
+            dh = ops.dropout_add(dh, None, self._site(snap, 0, hid))
         de = ops.add_layernorm_bwd(dh, e, None, self.P(pre + "embeddings.LayerNorm.weight"), mean0, rstd0,
                                    dg_out=self._grad(pre + "embeddings.LayerNorm.weight"),
                                    db_out=self._grad(pre + "embeddings.LayerNorm.bias"))[0]
@@ -207,7 +252,7 @@ class RobertaModelHip(_RobertaHip):
 
     def _outputs(self, tokens, attention_mask, keep):
         r, l = tokens.shape
-        h, saved = self._encode(tokens, attention_mask, keep)
+        h, saved = self._encode(tokens, attention_mask, keep, self._tick(tokens, keep))
         pooled = None
         x0 = None
         if self.has_pooler:
@@ -255,13 +300,24 @@ class RobertaForSequenceClassificationHip(_RobertaHip):
 
     def _outputs(self, tokens, attention_mask, keep):
         r, l = tokens.shape
-        h, saved = self._encode(tokens, attention_mask, keep)
+        snap = self._tick(tokens, keep)
+        h, saved = self._encode(tokens, attention_mask, keep, snap)
+        s_in, s_out = self._head_sites(snap)
         x0 = self._first_token(h, r, l)
+        if s_in is not None:
+            x0 = ops.dropout_add(x0, None, s_in)
         c1 = ops.tanh_fwd(ops.gemm_nt(x0, self.P("classifier.dense.weight"), self.P("classifier.dense.bias")))
-        logits = ops.gemm_nt(c1, self.P("classifier.out_proj.weight"), self.P("classifier.out_proj.bias"))
+        c1d = c1 if s_out is None else ops.dropout_add(c1, None, s_out)
+        logits = ops.gemm_nt(c1d, self.P("classifier.out_proj.weight"), self.P("classifier.out_proj.bias"))
         if keep:
-            self._saved = (saved, x0, c1)
+            self._saved = (saved, x0, c1)  # x0 after its dropout; the tanh's output before the second one
         return (logits,)
+
+    def _head_sites(self, snap):
+        """The head's two dropout sites (on h[:, 0], after the tanh); (None, None) without dropout."""
+        hid = None if snap is None else self._drop_hid
+        n = self.n_layer
+        return self._site(snap, 1 + 3 * n, hid), self._site(snap, 2 + 3 * n, hid)
 
     @torch.no_grad()
     def forward(self, input_ids, attention_mask=None, return_dict=True):
@@ -276,8 +332,14 @@ class RobertaForSequenceClassificationHip(_RobertaHip):
         saved, x0, c1 = self._saved
         self._saved = None
         r, l = saved[3], saved[4]
-        dc1 = self._linear_bwd("classifier.out_proj", c1, dlogits.contiguous())
+        s_in, s_out = self._head_sites(saved[-1])
+        c1d = c1 if s_out is None else ops.dropout_add(c1, None, s_out)  # out_proj's input, masked again
+        dc1 = self._linear_bwd("classifier.out_proj", c1d, dlogits.contiguous())
+        if s_out is not None:
+            dc1 = ops.dropout_add(dc1, None, s_out)
         dx0 = self._linear_bwd("classifier.dense", x0, ops.tanh_bwd(dc1, c1))
+        if s_in is not None:
+            dx0 = ops.dropout_add(dx0, None, s_in)
         dh = torch.zeros((r * l, self.d_model), dtype=torch.float32, device=dx0.device)
         dh.view(r, l, self.d_model)[:, 0] = dx0
         self._encode_bwd(saved, dh)

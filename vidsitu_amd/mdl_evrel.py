@@ -22,6 +22,13 @@ def _flat_tokens(toks, mask):
             mask.reshape(b * num_ev * num_seq_eg, seq_len).contiguous(), (b, num_ev, num_seq_eg))
 
 
+def _rob_dropout(cfg):
+    """`mdl.rob_dropout`: one number for RoBERTa's hidden and attention dropout (0.1 = what `from_pretrained` gives the
+    reference)."""
+    p = float(cfg.mdl.get("rob_dropout", 0.0))
+    return dict(hidden_dropout_prob=p, attention_probs_dropout_prob=p)
+
+
 class Simple_EvRel_Roberta(nn.Module):
     """`mdl_evrel.py:12-50` (`rob_evrel`): RoBERTa sequence classification (5 labels) over the paired SRL text
     `evrel_seq_out` [B, 4, n_ann, 120]."""
@@ -35,7 +42,7 @@ class Simple_EvRel_Roberta(nn.Module):
 
     def build_model(self):
         self.rob_mdl = hf_roberta.build(self.full_cfg.mdl.rob_mdl_name, RobertaForSequenceClassificationHip,
-                                        num_labels=5)
+                                        num_labels=5, **_rob_dropout(self.full_cfg))
 
     def forward(self, inp):
         src_toks, src_attn_mask, (B, num_ev, num_seq_eg) = _flat_tokens(inp["evrel_seq_out"],
@@ -60,7 +67,8 @@ class SFPret_SimpleEvRel(nn.Module):
         self.build_model()
 
     def build_model(self):
-        self.rob_mdl = hf_roberta.build(self.full_cfg.mdl.rob_mdl_name, RobertaModelHip, add_pooling_layer=True)
+        self.rob_mdl = hf_roberta.build(self.full_cfg.mdl.rob_mdl_name, RobertaModelHip, add_pooling_layer=True,
+                                        **_rob_dropout(self.full_cfg))
         head_dim = get_head_dim(self.full_cfg)
         hidden = self.rob_mdl.d_model  # 768 for roberta-base: the reference's 1792 = 1024 + 768
         self.vid_feat_encoder = HipMLP(nn.Linear(head_dim, 1024), nn.ReLU(), nn.Linear(1024, 1024))

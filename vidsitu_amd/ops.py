@@ -1617,19 +1617,25 @@ def _key_mask_u8(key_mask, r, l):
     return key_mask.contiguous()
 
 
-def attn_pad(qkv, key_mask, r, l, n_head):
-    """Bidirectional padding-masked self-attention: qkv f32 [R*L, 3D]; key_mask uint8 [R, L] or None -> f32 [R*L, D]."""
+def attn_pad(qkv, key_mask, r, l, n_head, drop=None):
+    """Bidirectional padding-masked self-attention: qkv f32 [R*L, 3D]; key_mask uint8 [R, L] or None -> f32 [R*L, D].
+    drop: dropout on the probabilities (see dropout_params above)."""
     qkv = _f32c(qkv)
     d = qkv.shape[1] // 3
     if qkv.shape[0] != r * l or qkv.shape[1] != 3 * d or d % n_head:
         raise _lib.VsError(f"attn_pad: qkv {tuple(qkv.shape)} is not [{r}*{l}, 3*D] with D % {n_head} == 0")
     out = torch.empty((r * l, d), dtype=torch.float32, device=qkv.device)
+    if drop is not None:
+        snap, site, thr, scale = drop
+        _lib.call("vs_attn_pad_drop_fwd", _ptr(qkv), _ptr(_key_mask_u8(key_mask, r, l)), _ptr(out), r, l, n_head,
+                  d // n_head, _ptr(snap), int(site), int(thr), float(scale), _stream())
+        return out
     _lib.call("vs_attn_pad_fwd", _ptr(qkv), _ptr(_key_mask_u8(key_mask, r, l)), _ptr(out), r, l, n_head,
               d // n_head, _stream())
     return out
 
 
-def attn_pad_bwd(qkv, key_mask, dout, r, l, n_head):
+def attn_pad_bwd(qkv, key_mask, dout, r, l, n_head, drop=None):
     qkv = _f32c(qkv)
     d = qkv.shape[1] // 3
     if qkv.shape[0] != r * l or dout.numel() != r * l * d or d % n_head:
@@ -1637,6 +1643,12 @@ def attn_pad_bwd(qkv, key_mask, dout, r, l, n_head):
     dqkv = torch.empty_like(qkv)
     need = _lib.load().vs_attn_pad_bwd_scratch_bytes(r, l, n_head)
     ws = _workspace(need, qkv.device)
+    if drop is not None:
+        snap, site, thr, scale = drop
+        _lib.call("vs_attn_pad_drop_bwd", _ptr(qkv), _ptr(_key_mask_u8(key_mask, r, l)), _ptr(_f32c(dout)),
+                  _ptr(dqkv), _ptr(ws), C.c_size_t(ws.numel()), r, l, n_head, d // n_head, _ptr(snap), int(site),
+                  int(thr), float(scale), _stream())
+        return dqkv
     _lib.call("vs_attn_pad_bwd", _ptr(qkv), _ptr(_key_mask_u8(key_mask, r, l)), _ptr(_f32c(dout)), _ptr(dqkv),
               _ptr(ws), C.c_size_t(ws.numel()), r, l, n_head, d // n_head, _stream())
     return dqkv

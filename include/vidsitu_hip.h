@@ -568,6 +568,16 @@ size_t vs_gemm_nt_f32_workspace_bytes(int M, int N, int K);
 int vs_gemm_nt_f32_ws(const float* x, const float* w, const float* b, const float* res, float* y, int M,
                       int N, int K, int act, void* workspace, size_t ws_bytes, void* stream);
 
+/* The same GEMM with bf16 operands and fp32 accumulation (v_mfma_f32_32x32x16_bf16), every M >= 1: x and w are
+ * fp32 in memory and each element is rounded to bf16 (nearest, ties to even) on its way into the tile -- no bf16
+ * copy of either tensor exists -- so y = act(sum_k fp32(bf16(x[m,k])) * fp32(bf16(w[n,k])) + b) + res with exact
+ * products, fp32 sums and an fp32 epilogue: it differs from an fp32 evaluation over the rounded operands by
+ * summation order only.  Tile choice, split-K through `workspace` (vs_gemm_nt_bf16_workspace_bytes; NULL, short or
+ * 0 bytes = unsplit) and the slice-ordered reduce are those of vs_gemm_nt_f32_ws: bitwise reproducible. */
+size_t vs_gemm_nt_bf16_workspace_bytes(int M, int N, int K);
+int vs_gemm_nt_bf16_ws(const float* x, const float* w, const float* b, const float* res, float* y, int M,
+                       int N, int K, int act, void* workspace, size_t ws_bytes, void* stream);
+
 /* Decode-step (1..64 rows) GEMM on fragment-major operands.  vs_pack_rows_f32 copies a row-major
  * matrix src[R][K] (K % 16 == 0) into 1-KB blocks of 16 rows x 16 floats in v_mfma_f32_16x16x4_f32
  * operand order (block (r/16, k/16) at index (r/16)*(K/16) + k/16; lane (k%16/4)*16 + r%16 holds floats

@@ -159,6 +159,7 @@ class CfgProcessor:
         # an addition of this project that the reference's own config file does not carry: that file still loads,
         # and the key can be overridden on top of it
         cfg.mdl.setdefault("gpt2_dropout", 0.0)
+        cfg.mdl.setdefault("gpt2_matmul", "fp32")
         cfg.mdl.setdefault("rob_dropout", 0.0)
         return cfg
 

@@ -139,17 +139,18 @@ class FlatParamModule(nn.Module):
             self._drop_state.copy_(new)
 
     # ---- backward of a dense layer ---------------------------------------------------------------------
-    def _linear_bwd(self, name, x, dy, bias=True, need_dx=True, conv1d=False):
+    def _linear_bwd(self, name, x, dy, bias=True, need_dx=True, conv1d=False, bf16=False):
         """y = x W^T + b with W [out, in]: dW = dy^T x, db = colsum(dy), dx = dy W.  conv1d: huggingface's Conv1D,
-        y = x W + b with W [in, out]: dW = x^T dy, and the parameter itself is the K-contiguous operand of dx."""
+        y = x W + b with W [in, out]: dW = x^T dy, and the parameter itself is the K-contiguous operand of dx.  bf16: both
+        GEMMs take bf16 operands (ops.gemm_nt); the bias gradient stays an fp32 column sum."""
         w = self.P(name + ".weight")
         a, b = (x, dy) if conv1d else (dy, x)
-        ops.gemm_nt(ops.transpose_f32(a), ops.transpose_f32(b), out=self._grad(name + ".weight"))
+        ops.gemm_nt(ops.transpose_f32(a), ops.transpose_f32(b), out=self._grad(name + ".weight"), bf16=bf16)
         if bias:
             ops.colsum_f32(dy, out=self._grad(name + ".bias"))
         if not need_dx:
             return None
-        return ops.gemm_nt(dy, w if conv1d else ops.transpose_f32(w))
+        return ops.gemm_nt(dy, w if conv1d else ops.transpose_f32(w), bf16=bf16)
 
     # ---- hand-over of the saved activations ------------------------------------------------------------
     def take_train_state(self):

@@ -22,6 +22,13 @@ counter generator of csrc/dropout_rng.h inside the kernels (nothing is stored: t
 step's snapshot of the persistent `[seed, step]` device state).  Eval, `forward_logits`, `forward_step` and generation
 never apply dropout and never advance the state.
 
+Mixed precision: `matmul="bf16"` (default `"fp32"`) gives the dense projections of the whole-sequence passes --
+`forward_train`, `backward`, `forward_logits`: c_attn, attn.c_proj, c_fc, mlp.c_proj and the tied lm_head, forward, dx
+and dW -- bf16 operands with fp32 accumulation (`ops.gemm_nt(bf16=True)`: the kernel rounds the fp32 operands as it
+loads them, no bf16 copy of a weight or activation exists).  Everything else -- parameters, Adam, layernorm, attention,
+gelu, residuals, dropout, the loss, bias and embedding gradients, and the whole cached decode step -- is fp32 in both
+modes, so the mode changes no generated token for given weights.
+
 `GPT2LMHeadModelHip` is a `flat_module.FlatParamModule`: registration, state dict, the cached weight copies and the
 autograd node (`FlatTrainFn`) live there; this file keeps the names / shapes, the arithmetic and `KVCacheState`.
 """
@@ -79,8 +86,12 @@ class GPT2LMHeadModelHip(FlatParamModule):
     _DROP_CAPTURE_MSG = "the GPT-2 dropout state must exist before a graph capture (run one eager step first)"
 
     def __init__(self, n_layer, d_model, n_head, n_positions, vocab_size, embd_pdrop=0.0, attn_pdrop=0.0,
-                 resid_pdrop=0.0):
+                 resid_pdrop=0.0, matmul="fp32"):
         super().__init__()
+        if matmul not in ("fp32", "bf16"):
+            raise ValueError(f'matmul must be "fp32" or "bf16", got {matmul!r}')
+        self.matmul = matmul
+        self._bf16 = matmul == "bf16"  # operand precision of the whole-sequence GEMMs (module docstring)
         self.n_layer, self.d_model, self.n_head, self.n_positions = n_layer, d_model, n_head, n_positions
         self.embd_pdrop, self.attn_pdrop, self.resid_pdrop = float(embd_pdrop), float(attn_pdrop), float(resid_pdrop)
         # (thr, scale) per probability, None at p = 0 (that site then runs today's launches); refuses p outside [0, 1)
@@ -155,21 +166,21 @@ class GPT2LMHeadModelHip(FlatParamModule):
         return self.P("transformer.wte.weight")
 
     # ---- compute ---------------------------------------------------------------------------
-    def _block(self, i, h, attn_fn):
+    def _block(self, i, h, attn_fn, bf16=False):
         q = f"transformer.h.{i}."
         a = ops.add_layernorm_fwd(h, None, self.P(q + "ln_1.weight"), self.P(q + "ln_1.bias"), 1e-5)[0]
-        qkv = ops.gemm_nt(a, self._w(q + "attn.c_attn.weight"), self.P(q + "attn.c_attn.bias"))
+        qkv = ops.gemm_nt(a, self._w(q + "attn.c_attn.weight"), self.P(q + "attn.c_attn.bias"), bf16=bf16)
         o = attn_fn(i, qkv)
-        h = ops.gemm_nt(o, self._w(q + "attn.c_proj.weight"), self.P(q + "attn.c_proj.bias"), res=h)
+        h = ops.gemm_nt(o, self._w(q + "attn.c_proj.weight"), self.P(q + "attn.c_proj.bias"), res=h, bf16=bf16)
         m = ops.add_layernorm_fwd(h, None, self.P(q + "ln_2.weight"), self.P(q + "ln_2.bias"), 1e-5)[0]
         f = ops.gemm_nt(m, self._w(q + "mlp.c_fc.weight"), self.P(q + "mlp.c_fc.bias"),
-                        act=ops.ACT_GELU_NEW)
-        return ops.gemm_nt(f, self._w(q + "mlp.c_proj.weight"), self.P(q + "mlp.c_proj.bias"), res=h)
+                        act=ops.ACT_GELU_NEW, bf16=bf16)
+        return ops.gemm_nt(f, self._w(q + "mlp.c_proj.weight"), self.P(q + "mlp.c_proj.bias"), res=h, bf16=bf16)
 
-    def _head(self, h):
+    def _head(self, h, bf16=False):
         hf = ops.add_layernorm_fwd(h, None, self.P("transformer.ln_f.weight"),
                                    self.P("transformer.ln_f.bias"), 1e-5)[0]
-        return ops.gemm_nt(hf, self.P("transformer.wte.weight"))
+        return ops.gemm_nt(hf, self.P("transformer.wte.weight"), bf16=bf16)
 
     @torch.no_grad()
     def forward_logits(self, tokens, attention_mask=None):
@@ -180,8 +191,8 @@ class GPT2LMHeadModelHip(FlatParamModule):
         km = None if attention_mask is None else attention_mask.to(torch.uint8).contiguous()
         h = ops.gpt2_embed(tokens, self.P("transformer.wte.weight"), self.P("transformer.wpe.weight"))
         for i in range(self.n_layer):
-            h = self._block(i, h, lambda _i, qkv: ops.attn_causal(qkv, km, r, l, self.n_head))
-        return self._head(h).view(r, l, -1)
+            h = self._block(i, h, lambda _i, qkv: ops.attn_causal(qkv, km, r, l, self.n_head), bf16=self._bf16)
+        return self._head(h, bf16=self._bf16).view(r, l, -1)
 
     @torch.no_grad()
     def forward_step(self, last_tokens, state: KVCacheState, key_mask=None, max_len=None):
@@ -280,19 +291,19 @@ class GPT2LMHeadModelHip(FlatParamModule):
             q = f"transformer.h.{i}."
             a, mean1, rstd1 = ops.add_layernorm_fwd(h, None, self.P(q + "ln_1.weight"),
                                                     self.P(q + "ln_1.bias"), 1e-5)
-            qkv = ops.gemm_nt(a, self._w(q + "attn.c_attn.weight"), self.P(q + "attn.c_attn.bias"))
+            qkv = ops.gemm_nt(a, self._w(q + "attn.c_attn.weight"), self.P(q + "attn.c_attn.bias"), bf16=self._bf16)
             o = ops.attn_causal(qkv, km, r, l, self.n_head, drop=self._site(snap, 1 + 3 * i, self._drop_attn))
             h_mid = self._proj_res(q + "attn.c_proj", o, h, self._site(snap, 2 + 3 * i, self._drop_resid))
             m, mean2, rstd2 = ops.add_layernorm_fwd(h_mid, None, self.P(q + "ln_2.weight"),
                                                     self.P(q + "ln_2.bias"), 1e-5)
-            f_pre = ops.gemm_nt(m, self._w(q + "mlp.c_fc.weight"), self.P(q + "mlp.c_fc.bias"))
+            f_pre = ops.gemm_nt(m, self._w(q + "mlp.c_fc.weight"), self.P(q + "mlp.c_fc.bias"), bf16=self._bf16)
             f = ops.gelu_new_fwd(f_pre)
             h_out = self._proj_res(q + "mlp.c_proj", f, h_mid, self._site(snap, 3 + 3 * i, self._drop_resid))
             layers.append((h, a, mean1, rstd1, qkv, o, h_mid, m, mean2, rstd2, f_pre, f))
             h = h_out
         hf, meanf, rstdf = ops.add_layernorm_fwd(h, None, self.P("transformer.ln_f.weight"),
                                                  self.P("transformer.ln_f.bias"), 1e-5)
-        logits = ops.gemm_nt(hf, self.P("transformer.wte.weight"))
+        logits = ops.gemm_nt(hf, self.P("transformer.wte.weight"), bf16=self._bf16)
         self._saved = (tokens, km, r, l, layers, h, hf, meanf, rstdf, snap)
         return logits.view(r, l, -1)
 
@@ -300,8 +311,9 @@ class GPT2LMHeadModelHip(FlatParamModule):
         """res + dropout(x W + b): at a dropout site the GEMM runs without the residual and the mask kernel adds it
         (the GEMM epilogues and the split-K reduce stay as they are)."""
         if drop is None:
-            return ops.gemm_nt(x, self._w(name + ".weight"), self.P(name + ".bias"), res=res)
-        return ops.dropout_add(ops.gemm_nt(x, self._w(name + ".weight"), self.P(name + ".bias")), res, drop)
+            return ops.gemm_nt(x, self._w(name + ".weight"), self.P(name + ".bias"), res=res, bf16=self._bf16)
+        return ops.dropout_add(ops.gemm_nt(x, self._w(name + ".weight"), self.P(name + ".bias"), bf16=self._bf16),
+                               res, drop)
 
     @torch.no_grad()
     def backward(self, dlogits):
@@ -312,8 +324,8 @@ class GPT2LMHeadModelHip(FlatParamModule):
         dlogits = dlogits.reshape(r * l, -1)
         # tied lm_head: logits = hf @ wte^T
         dwte = self._grad("transformer.wte.weight")
-        ops.gemm_nt(ops.transpose_f32(dlogits), ops.transpose_f32(hf), out=dwte)
-        dhf = ops.gemm_nt(dlogits, ops.transpose_f32(wte))
+        ops.gemm_nt(ops.transpose_f32(dlogits), ops.transpose_f32(hf), out=dwte, bf16=self._bf16)
+        dhf = ops.gemm_nt(dlogits, ops.transpose_f32(wte), bf16=self._bf16)
         dh, _, _, _ = ops.add_layernorm_bwd(dhf, h_last, None, self.P("transformer.ln_f.weight"), meanf,
                                             rstdf, dg_out=self._grad("transformer.ln_f.weight"),
                                             db_out=self._grad("transformer.ln_f.bias"))
@@ -323,17 +335,18 @@ class GPT2LMHeadModelHip(FlatParamModule):
             s_attn, s_proj, s_mlp = (self._site(snap, k + 3 * i, p) for k, p in
                                      ((1, self._drop_attn), (2, self._drop_resid), (3, self._drop_resid)))
             df = self._linear_bwd(q + "mlp.c_proj", f, dh if s_mlp is None else ops.dropout_add(dh, None, s_mlp),
-                                  conv1d=True)
+                                  conv1d=True, bf16=self._bf16)
             df_pre = ops.gelu_new_bwd(df, f_pre)
-            dm = self._linear_bwd(q + "mlp.c_fc", m, df_pre, conv1d=True)
+            dm = self._linear_bwd(q + "mlp.c_fc", m, df_pre, conv1d=True, bf16=self._bf16)
             dmid_ln, _, _, _ = ops.add_layernorm_bwd(dm, h_mid, None, self.P(q + "ln_2.weight"), mean2, rstd2,
                                                      dg_out=self._grad(q + "ln_2.weight"),
                                                      db_out=self._grad(q + "ln_2.bias"))
             d_mid = ops.add_f32(dh, dmid_ln)
             do = self._linear_bwd(q + "attn.c_proj", o,
-                                  d_mid if s_proj is None else ops.dropout_add(d_mid, None, s_proj), conv1d=True)
+                                  d_mid if s_proj is None else ops.dropout_add(d_mid, None, s_proj), conv1d=True,
+                                  bf16=self._bf16)
             dqkv = ops.attn_causal_bwd(qkv, km, do, r, l, self.n_head, drop=s_attn)
-            da = self._linear_bwd(q + "attn.c_attn", a, dqkv, conv1d=True)
+            da = self._linear_bwd(q + "attn.c_attn", a, dqkv, conv1d=True, bf16=self._bf16)
             din_ln, _, _, _ = ops.add_layernorm_bwd(da, h_in, None, self.P(q + "ln_1.weight"), mean1, rstd1,
                                                     dg_out=self._grad(q + "ln_1.weight"),
                                                     db_out=self._grad(q + "ln_1.bias"))
@@ -384,7 +397,9 @@ class HuggingFaceGPT2Decoder(nn.Module):
         # one number for the three probabilities, as hf_gpt2_fseq.py:144-146 intended; absent in the reference's
         # own config file, hence the default
         pdrop = float(args.mdl.get("gpt2_dropout", 0.0))
-        self.model = GPT2LMHeadModelHip(*dims, embd_pdrop=pdrop, attn_pdrop=pdrop, resid_pdrop=pdrop)
+        # "fp32" | "bf16": operand precision of the whole-sequence GEMMs (this project's own switch)
+        self.model = GPT2LMHeadModelHip(*dims, embd_pdrop=pdrop, attn_pdrop=pdrop, resid_pdrop=pdrop,
+                                        matmul=str(args.mdl.get("gpt2_matmul", "fp32")))
         if state_dict is not None:
             self.model.load_state_dict(state_dict)
         self.voc_size = len(dictionary)

@@ -1169,14 +1169,21 @@ def cast_bf16(src_f32, dst_bf16):
 ACT_NONE, ACT_RELU, ACT_GELU_NEW = 0, 1, 2
 
 
-def gemm_nt(x, w, b=None, res=None, act=ACT_NONE, out=None):
-    """act(x[M,K] @ w[N,K]^T + b) + res, fp32."""
+def gemm_nt(x, w, b=None, res=None, act=ACT_NONE, out=None, bf16=False):
+    """act(x[M,K] @ w[N,K]^T + b) + res, fp32.  bf16: the operands (fp32 in memory) are rounded to bf16 inside the
+    kernel and multiplied on the bf16 matrix cores; accumulation, epilogue and result stay fp32."""
     x, w = _f32c(x), _f32c(w)
     m, k = x.shape
     n = w.shape[0]
     if w.shape[1] != k:
         raise _lib.VsError(f"gemm_nt: K mismatch {tuple(x.shape)} x {tuple(w.shape)}")
     y = torch.empty((m, n), dtype=torch.float32, device=x.device) if out is None else out
+    if bf16:
+        need = _lib.load().vs_gemm_nt_bf16_workspace_bytes(m, n, k)
+        ws = _workspace(need, x.device) if need else None
+        _lib.call("vs_gemm_nt_bf16_ws", _ptr(x), _ptr(w), _ptr(b), _ptr(res), _ptr(y), m, n, k, int(act),
+                  _ptr(ws), C.c_size_t(ws.numel() if need else 0), _stream())
+        return y
     need = _lib.load().vs_gemm_nt_f32_workspace_bytes(m, n, k) if m > 64 else 0
     if need:
         ws = _workspace(need, x.device)

@@ -1,4 +1,4 @@
-"""LDS bank-conflict simulation of gemm_nt_bf16_kernel's tile image (csrc/gpt2_ops.hip): K-major bf16 rows of 32 elements
+"""LDS bank-conflict simulation of the GemmBf16 tile image of gemm_nt_kernel (csrc/gemm_nt.hip): K-major bf16 rows of 32 elements
 under candidate row pitches.  Reads: one ds_read_b128 per lane and 16-wide k-step (row = lane & 31 of a 32-row block,
 k = 16 * step + 8 * (lane >> 5)); writes: the loader's 8-byte tile stores (thread t: row t >> 3 of a 32-row pass,
 k = 4 * (t & 7)).  Lane groups and bank rules are MI355X_MICROARCH.md's (LDS table).  1.00 = conflict free.

@@ -71,6 +71,16 @@ __device__ __forceinline__ uint4 pack8_bf16(const float* f) {
   return v;
 }
 
+// transformers activations.gelu_new
+__device__ __forceinline__ float gelu_new_f(float x) {
+  return 0.5f * x * (1.0f + tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x)));
+}
+
+// y = act(x . w^T + b) + res on the fp32 matrix cores (gemm_nt.hip), for vs_gemm_nt_f32 (txenc_ops.hip) above 64 rows;
+// split-K only with a workspace of vs_gemm_nt_f32_workspace_bytes(M, N, K)
+int vs_gemm_nt_f32_mfma(const float* x, const float* w, const float* b, const float* res, float* y, int M, int N,
+                        int K, int act, hipStream_t st, void* ws = nullptr, size_t ws_bytes = 0);
+
 // x = q * d + r for 0 <= x < 2^24, rcp = 1.0f / d (float quotient, two fix-ups): ~8 instructions where a runtime
 // 32-bit integer division is ~40 and a 64-bit one ~100+
 __device__ __forceinline__ void fast_divmod(int x, int d, float rcp, int& q, int& r) {

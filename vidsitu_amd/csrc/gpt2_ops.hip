@@ -2,402 +2,12 @@
 // arguments with -- vidsitu_code/hf_gpt2_fseq.py:124-215 (huggingface GPT2LMHeadModel:
 // Conv1D projections, causal + key-padding attention, gelu_new MLP, tied lm_head) -- and the
 // per-step scoring of its beam search (vidsitu_code/seq_gen.py:310-385 + fairseq BeamSearch.step).
-// All arithmetic is fp32 like the reference (no AMP anywhere): dense projections
-// run on the fp32 matrix cores (v_mfma_f32_32x32x2_f32, 157 TFLOP/s dense on MI355X) when there
-// are more than 64 rows and as weight-streaming dot products (txenc_ops.hip) below that.  One opt-in
-// exception: gemm_nt_bf16_kernel (bf16 operands rounded in the loader, fp32 accumulation) for the
-// whole-sequence passes of a model built with matmul="bf16".
+// All arithmetic is fp32 like the reference (no AMP anywhere).  The dense projections
+// are gemm_nt.hip's.
 #include <math.h>
 
 #include "common.h"
 #include "dropout_rng.h"
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-__device__ __forceinline__ float gelu_new_f(float x) {
-  // transformers activations.gelu_new
-  return 0.5f * x * (1.0f + tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x)));
-}
-
-// ----------------------------------------------------------------------------
-// y[M,N] = act(x[M,K] . w[N,K]^T + b) + res      ("NT": both operands K-contiguous)
-// 128x128x32 (or 64x64x32) tile, 4 waves as 2x2, each wave a block of 32x32 MFMA accumulators.
-// LDS rows are K-major with an odd pitch (33 floats): the fragment read of a 32x32x2 MFMA
-// (lane l: row l&31, k = l>>5) is then conflict free.  Register-staged double buffer.
-// ----------------------------------------------------------------------------
-#define GM_BK 32
-#define GM_LD 33
-
-// Epilogue of one wave's MR x NR block of 32x32 accumulators (shared by the fp32 and the bf16-operand kernel: the D
-// layout of a 32x32 MFMA does not depend on the operand type): col = lane & 31, row = 8*(e/4) + 4*(lane>>5) + (e&3).
-// raw: a split-K slice stores its partial tile as it is (y already points at the slice's slab).
-template <int BM, int BN>
-__device__ __forceinline__ void gemm_tile_epilogue(const f32x16 (&acc)[BM / 64][BN / 64], const float* __restrict__ bias,
-                                                   const float* res, float* y, int M, int N, int mw, int nw, int lane,
-                                                   int act, bool raw) {
-#pragma unroll
-  for (int a = 0; a < BM / 64; ++a)
-#pragma unroll
-    for (int b = 0; b < BN / 64; ++b) {
-      const int n = nw + b * 32 + (lane & 31);
-      if (n >= N) continue;
-      if (raw) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int m = mw + a * 32 + 8 * (e >> 2) + 4 * (lane >> 5) + (e & 3);
-          if (m < M) y[(long long)m * N + n] = acc[a][b][e];
-        }
-        continue;
-      }
-      const float bvv = bias ? bias[n] : 0.f;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int m = mw + a * 32 + 8 * (e >> 2) + 4 * (lane >> 5) + (e & 3);
-        if (m < M) {
-          float v = acc[a][b][e] + bvv;
-          if (act == 1) v = fmaxf(v, 0.f);
-          else if (act == 2) v = gelu_new_f(v);
-          if (res) v += res[(long long)m * N + n];
-          y[(long long)m * N + n] = v;
-        }
-      }
-    }
-}
-
-// Split-K (gridDim.z = S > 1): slice z covers k-tiles [z * kts, (z + 1) * kts) and stores its raw partial
-// tile into slab z of `y` (M * N floats each); gemm_splitk_reduce_kernel adds the slabs in slice order and
-// applies the epilogue.  Layers with few output tiles (600 x 1024: 160 tiles of 64 x 64 for 256 CUs) then
-// run 3-4 blocks per CU and overlap each other's memory latency.
-template <int BM, int BN, bool KVEC>  // 128x128 (2x2 MFMA tiles per wave) or 64x64 (one per wave); K % 4 == 0
-__global__ __launch_bounds__(256) void gemm_nt_f32_kernel(const float* __restrict__ x,
-                                                          const float* __restrict__ w,
-                                                          const float* __restrict__ bias,
-                                                          const float* res, float* y, int M, int N,
-                                                          int K, int act, int kts) {
-  constexpr int MR = BM / 64, NR = BN / 64;  // 32x32 accumulators per wave
-  constexpr int PA = BM / 32, PB = BN / 32;  // loader passes (32 rows each)
-  __shared__ float As[2][BM * GM_LD];
-  __shared__ float Bs[2][BN * GM_LD];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-  // loader mapping: 8 float4 per 32-float row, 32 rows per pass
-  const int lc = tid & 7, lr = tid >> 3;
-  constexpr bool kvec = KVEC;  // compile time: a runtime flag put every load behind a branch (and a wait)
-  float4 ra[PA], rb[PB];
-
-  // Loads are branch-free (a load inside `if (ok)` sits in its own basic block behind its own wait: the 8
-  // loads of a k-tile were 8 serialised round trips) and RAW: out-of-range lanes read element 0 and are
-  // zeroed only when the tile is written to LDS, so nothing touches the loaded registers -- and no wait is
-  // placed -- before the MFMAs of the current tile have been issued.
-  unsigned okmask = 0;
-  auto ld4 = [&](const float* base, int row, int rows, int k, int bit) __attribute__((always_inline)) {
-    const bool ok = row < rows && k < K;
-    okmask = ok ? (okmask | (1u << bit)) : (okmask & ~(1u << bit));
-    if constexpr (kvec) return *(const float4*)(base + (ok ? (long long)row * K + k : 0));
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ok) {
-      const float* s = base + (long long)row * K + k;
-      v.x = s[0]; if (k + 1 < K) v.y = s[1]; if (k + 2 < K) v.z = s[2]; if (k + 3 < K) v.w = s[3];
-    }
-    return v;
-  };
-  auto gload = [&](int k0) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < PA; ++i) ra[i] = ld4(x, m0 + lr + 32 * i, M, k0 + lc * 4, i);
-#pragma unroll
-    for (int i = 0; i < PB; ++i) rb[i] = ld4(w, n0 + lr + 32 * i, N, k0 + lc * 4, PA + i);
-  };
-  auto sstore = [&](int buf) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < PA; ++i) {
-      float* a = &As[buf][(lr + 32 * i) * GM_LD + lc * 4];
-      const bool ok = (okmask >> i) & 1;
-      a[0] = ok ? ra[i].x : 0.f; a[1] = ok ? ra[i].y : 0.f; a[2] = ok ? ra[i].z : 0.f; a[3] = ok ? ra[i].w : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < PB; ++i) {
-      float* b = &Bs[buf][(lr + 32 * i) * GM_LD + lc * 4];
-      const bool ok = (okmask >> (PA + i)) & 1;
-      b[0] = ok ? rb[i].x : 0.f; b[1] = ok ? rb[i].y : 0.f; b[2] = ok ? rb[i].z : 0.f; b[3] = ok ? rb[i].w : 0.f;
-    }
-  };
-
-  f32x16 acc[MR][NR];
-#pragma unroll
-  for (int a = 0; a < MR; ++a)
-#pragma unroll
-    for (int b = 0; b < NR; ++b)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
-
-  const int fr = lane & 31, fk = lane >> 5;
-  const int nk_all = (K + GM_BK - 1) / GM_BK;
-  const bool split = gridDim.z > 1;
-  const int kt0 = split ? blockIdx.z * kts : 0;
-  const int nk = split ? min(nk_all, kt0 + kts) : nk_all;
-  if (split) y += (long long)blockIdx.z * M * N;
-  gload(kt0 * GM_BK);
-  sstore(kt0 & 1);
-  __syncthreads();
-  for (int kt = kt0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) gload((kt + 1) * GM_BK);
-    const float* A = &As[cur][(wm * (BM / 2) + fr) * GM_LD + fk];
-    const float* B = &Bs[cur][(wn * (BN / 2) + fr) * GM_LD + fk];
-#pragma unroll
-    for (int ks = 0; ks < GM_BK; ks += 2) {
-      float av[MR], bv[NR];
-#pragma unroll
-      for (int a = 0; a < MR; ++a) av[a] = A[a * 32 * GM_LD + ks];
-#pragma unroll
-      for (int b = 0; b < NR; ++b) bv[b] = B[b * 32 * GM_LD + ks];
-#pragma unroll
-      for (int a = 0; a < MR; ++a)
-#pragma unroll
-        for (int b = 0; b < NR; ++b)
-          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a], bv[b], acc[a][b], 0, 0, 0);
-    }
-    if (kt + 1 < nk) sstore(cur ^ 1);
-    __syncthreads();
-  }
-  gemm_tile_epilogue<BM, BN>(acc, bias, res, y, M, N, m0 + wm * (BM / 2), n0 + wn * (BN / 2), lane, act, split);
-}
-
-__global__ void gemm_splitk_reduce_kernel(const float* slabs, const float* bias, const float* res, float* y,
-                                          long long MN, int N, int S, int act) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < MN; i += (long long)gridDim.x * blockDim.x) {
-    float v = slabs[i];
-    for (int s2 = 1; s2 < S; ++s2) v += slabs[(long long)s2 * MN + i];
-    if (bias) v += bias[i % N];
-    if (act == 1) v = fmaxf(v, 0.f);
-    else if (act == 2) v = gelu_new_f(v);
-    if (res) v += res[i];
-    y[i] = v;
-  }
-}
-
-// K slices for a GEMM with few output tiles: about 700 blocks, at least 4 k-tiles (128 floats) per slice
-static int gemm_split(int M, int N, int K) {
-  const long long t128 = (long long)((M + 127) / 128) * ((N + 127) / 128);
-  if (t128 >= 256) return 1;
-  const long long t64 = (long long)((M + 63) / 64) * ((N + 63) / 64);
-  const int nk = (K + GM_BK - 1) / GM_BK;
-  int S = (int)(704 / t64);
-  if (S > nk / 4) S = nk / 4;
-  if (S > 16) S = 16;
-  return S < 2 ? 1 : S;
-}
-
-extern "C" size_t vs_gemm_nt_f32_workspace_bytes(int M, int N, int K) {
-  if (M <= 64) return 0;
-  const int S = gemm_split(M, N, K);
-  return S > 1 ? (size_t)S * M * N * sizeof(float) : 0;
-}
-
-int vs_gemm_nt_f32_mfma(const float* x, const float* w, const float* b, const float* res, float* y,
-                        int M, int N, int K, int act, hipStream_t st, void* ws = nullptr, size_t ws_bytes = 0) {
-  // fewer than one 128x128 tile per CU: 64x64 tiles (4x the blocks) keep the chip busy
-  const long long t128 = (long long)((M + 127) / 128) * ((N + 127) / 128);
-  const bool kv = (K & 3) == 0 && ((((uintptr_t)x | (uintptr_t)w)) & 15) == 0;
-  if (t128 >= 256) {
-    if (kv)
-      hipLaunchKernelGGL((gemm_nt_f32_kernel<128, 128, true>), dim3((N + 127) / 128, (M + 127) / 128),
-                         dim3(256), 0, st, x, w, b, res, y, M, N, K, act, 0);
-    else
-      hipLaunchKernelGGL((gemm_nt_f32_kernel<128, 128, false>), dim3((N + 127) / 128, (M + 127) / 128),
-                         dim3(256), 0, st, x, w, b, res, y, M, N, K, act, 0);
-    VS_CHECK_LAUNCH();
-    return VS_OK;
-  }
-  const int S = ws ? gemm_split(M, N, K) : 1;
-  if (S > 1 && ws_bytes >= (size_t)S * M * N * sizeof(float)) {
-    const int nk = (K + GM_BK - 1) / GM_BK;
-    const int kts = (nk + S - 1) / S;
-    const int Se = (nk + kts - 1) / kts;  // slices that own at least one k-tile
-    if (kv)
-      hipLaunchKernelGGL((gemm_nt_f32_kernel<64, 64, true>), dim3((N + 63) / 64, (M + 63) / 64, Se), dim3(256),
-                         0, st, x, w, (const float*)nullptr, (const float*)nullptr, (float*)ws, M, N, K, 0, kts);
-    else
-      hipLaunchKernelGGL((gemm_nt_f32_kernel<64, 64, false>), dim3((N + 63) / 64, (M + 63) / 64, Se), dim3(256),
-                         0, st, x, w, (const float*)nullptr, (const float*)nullptr, (float*)ws, M, N, K, 0, kts);
-    const long long MN = (long long)M * N;
-    long long grid = (MN + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)grid), dim3(256), 0, st, (const float*)ws, b,
-                       res, y, MN, N, Se, act);
-  } else if (kv) {
-    hipLaunchKernelGGL((gemm_nt_f32_kernel<64, 64, true>), dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0,
-                       st, x, w, b, res, y, M, N, K, act, 0);
-  } else {
-    hipLaunchKernelGGL((gemm_nt_f32_kernel<64, 64, false>), dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0,
-                       st, x, w, b, res, y, M, N, K, act, 0);
-  }
-  VS_CHECK_LAUNCH();
-  return VS_OK;
-}
-
-/* vs_gemm_nt_f32 with a split-K workspace (vs_gemm_nt_f32_workspace_bytes(M, N, K); 0 = not needed). */
-extern "C" int vs_gemm_nt_f32_ws(const float* x, const float* w, const float* b, const float* res, float* y,
-                                 int M, int N, int K, int act, void* workspace, size_t ws_bytes, void* stream) {
-  VS_CHECK_ARG(x && w && y && M > 0 && N > 0 && K > 0, "bad args");
-  VS_CHECK_ARG(act >= 0 && act <= 2, "act must be 0 (none), 1 (relu) or 2 (gelu_new)");
-  if (M <= 64 || !workspace) return vs_gemm_nt_f32(x, w, b, res, y, M, N, K, act, stream);
-  return vs_gemm_nt_f32_mfma(x, w, b, res, y, M, N, K, act, (hipStream_t)stream, workspace, ws_bytes);
-}
-
-// ----------------------------------------------------------------------------
-// The same GEMM with bf16 operands (opt-in mixed precision of the whole-sequence passes): x and w stay fp32 in
-// memory; the loader rounds each element to bf16 (nearest, ties to even: v_cvt_pk_bf16_f32) where it writes the
-// tile to LDS, and the main loop runs v_mfma_f32_32x32x16_bf16 with fp32 accumulators.  bf16 x bf16 products are
-// exact in fp32, so the result differs from an fp32 GEMM over the rounded operands by summation order only.  Same
-// tiles, same 32-wide k-tile, same split-K slabs and reduce, same epilogue as the fp32 kernel above.
-//
-// LDS rows are K-major bf16 with a pitch of 40 elements = 80 bytes (the 64 bytes of a k-tile + one 16-byte slot).
-// A lane's fragment (row lane & 31, k = 16 * step + 8 * (lane >> 5) .. + 7) is one ds_read_b128 at 16-byte slot
-// 5 * row + 2 * step + (lane >> 5).  ds_read_b128 is served in four groups of 16 lanes (MI355X: {0-3, 12-15, 20-27},
-// {4-11, 16-19, 28-31} and the same + 32); the rows of a group cover every residue mod 16 once and share lane >> 5,
-// and 5 is odd, so its 16 slots are the 16 distinct slots of the 256-byte bank row: conflict free
-// (tools/probes/gemm_bf16_lds_sim.py counts it, and the 2-way conflicts the 8-byte tile stores keep).
-// ----------------------------------------------------------------------------
-#define GB_LD 40
-
-template <int BM, int BN, bool KVEC>  // as gemm_nt_f32_kernel
-__global__ __launch_bounds__(256) void gemm_nt_bf16_kernel(const float* __restrict__ x,
-                                                           const float* __restrict__ w,
-                                                           const float* __restrict__ bias,
-                                                           const float* res, float* y, int M, int N,
-                                                           int K, int act, int kts) {
-  constexpr int MR = BM / 64, NR = BN / 64;
-  constexpr int PA = BM / 32, PB = BN / 32;
-  __shared__ __attribute__((aligned(16))) uint16_t As[2][BM * GB_LD];
-  __shared__ __attribute__((aligned(16))) uint16_t Bs[2][BN * GB_LD];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-  const int lc = tid & 7, lr = tid >> 3;
-  constexpr bool kvec = KVEC;
-  float4 ra[PA], rb[PB];
-
-  // branch-free raw loads, zeroed at the LDS store: see gemm_nt_f32_kernel
-  unsigned okmask = 0;
-  auto ld4 = [&](const float* base, int row, int rows, int k, int bit) __attribute__((always_inline)) {
-    const bool ok = row < rows && k < K;
-    okmask = ok ? (okmask | (1u << bit)) : (okmask & ~(1u << bit));
-    if constexpr (kvec) return *(const float4*)(base + (ok ? (long long)row * K + k : 0));
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ok) {
-      const float* s = base + (long long)row * K + k;
-      v.x = s[0]; if (k + 1 < K) v.y = s[1]; if (k + 2 < K) v.z = s[2]; if (k + 3 < K) v.w = s[3];
-    }
-    return v;
-  };
-  auto gload = [&](int k0) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < PA; ++i) ra[i] = ld4(x, m0 + lr + 32 * i, M, k0 + lc * 4, i);
-#pragma unroll
-    for (int i = 0; i < PB; ++i) rb[i] = ld4(w, n0 + lr + 32 * i, N, k0 + lc * 4, PA + i);
-  };
-  auto st4 = [&](uint16_t* dst, const float4& r, bool ok) __attribute__((always_inline)) {
-    uint2 v;
-    v.x = pack2_bf16(ok ? r.x : 0.f, ok ? r.y : 0.f);
-    v.y = pack2_bf16(ok ? r.z : 0.f, ok ? r.w : 0.f);
-    *(uint2*)dst = v;
-  };
-  auto sstore = [&](int buf) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < PA; ++i) st4(&As[buf][(lr + 32 * i) * GB_LD + lc * 4], ra[i], (okmask >> i) & 1);
-#pragma unroll
-    for (int i = 0; i < PB; ++i) st4(&Bs[buf][(lr + 32 * i) * GB_LD + lc * 4], rb[i], (okmask >> (PA + i)) & 1);
-  };
-
-  f32x16 acc[MR][NR];
-#pragma unroll
-  for (int a = 0; a < MR; ++a)
-#pragma unroll
-    for (int b = 0; b < NR; ++b)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
-
-  const int fr = lane & 31, fk = lane >> 5;
-  const int nk_all = (K + GM_BK - 1) / GM_BK;
-  const bool split = gridDim.z > 1;
-  const int kt0 = split ? blockIdx.z * kts : 0;
-  const int nk = split ? min(nk_all, kt0 + kts) : nk_all;
-  if (split) y += (long long)blockIdx.z * M * N;
-  gload(kt0 * GM_BK);
-  sstore(kt0 & 1);
-  __syncthreads();
-  for (int kt = kt0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) gload((kt + 1) * GM_BK);
-    const uint16_t* A = &As[cur][(wm * (BM / 2) + fr) * GB_LD + fk * 8];
-    const uint16_t* B = &Bs[cur][(wn * (BN / 2) + fr) * GB_LD + fk * 8];
-#pragma unroll
-    for (int ks = 0; ks < GM_BK; ks += 16) {
-      bf16x8 av[MR], bv[NR];
-#pragma unroll
-      for (int a = 0; a < MR; ++a) av[a] = *(const bf16x8*)(A + a * 32 * GB_LD + ks);
-#pragma unroll
-      for (int b = 0; b < NR; ++b) bv[b] = *(const bf16x8*)(B + b * 32 * GB_LD + ks);
-#pragma unroll
-      for (int a = 0; a < MR; ++a)
-#pragma unroll
-        for (int b = 0; b < NR; ++b)
-          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[a], bv[b], acc[a][b], 0, 0, 0);
-    }
-    if (kt + 1 < nk) sstore(cur ^ 1);
-    __syncthreads();
-  }
-  gemm_tile_epilogue<BM, BN>(acc, bias, res, y, M, N, m0 + wm * (BM / 2), n0 + wn * (BN / 2), lane, act, split);
-}
-
-template <int BM, int BN>
-static void gemm_nt_bf16_launch(bool kv, dim3 grid, hipStream_t st, const float* x, const float* w, const float* b,
-                                const float* res, float* y, int M, int N, int K, int act, int kts) {
-  if (kv)
-    hipLaunchKernelGGL((gemm_nt_bf16_kernel<BM, BN, true>), grid, dim3(256), 0, st, x, w, b, res, y, M, N, K, act, kts);
-  else
-    hipLaunchKernelGGL((gemm_nt_bf16_kernel<BM, BN, false>), grid, dim3(256), 0, st, x, w, b, res, y, M, N, K, act,
-                       kts);
-}
-
-extern "C" size_t vs_gemm_nt_bf16_workspace_bytes(int M, int N, int K) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const int S = gemm_split(M, N, K);
-  return S > 1 ? (size_t)S * M * N * sizeof(float) : 0;
-}
-
-/* y = act(bf16(x) . bf16(w)^T + b) + res with fp32 accumulation, every M >= 1; tile choice and split-K as
- * vs_gemm_nt_f32_ws (a missing or short workspace runs the unsplit 64x64 kernel). */
-extern "C" int vs_gemm_nt_bf16_ws(const float* x, const float* w, const float* b, const float* res, float* y,
-                                  int M, int N, int K, int act, void* workspace, size_t ws_bytes, void* stream) {
-  VS_CHECK_ARG(x && w && y && M > 0 && N > 0 && K > 0, "bad args");
-  VS_CHECK_ARG(act >= 0 && act <= 2, "act must be 0 (none), 1 (relu) or 2 (gelu_new)");
-  hipStream_t st = (hipStream_t)stream;
-  const long long t128 = (long long)((M + 127) / 128) * ((N + 127) / 128);
-  const bool kv = (K & 3) == 0 && ((((uintptr_t)x | (uintptr_t)w)) & 15) == 0;
-  const dim3 g64((N + 63) / 64, (M + 63) / 64);
-  const int S = workspace && t128 < 256 ? gemm_split(M, N, K) : 1;
-  if (t128 >= 256) {
-    gemm_nt_bf16_launch<128, 128>(kv, dim3((N + 127) / 128, (M + 127) / 128), st, x, w, b, res, y, M, N, K, act, 0);
-  } else if (S > 1 && ws_bytes >= (size_t)S * M * N * sizeof(float)) {
-    const int nk = (K + GM_BK - 1) / GM_BK;
-    const int kts = (nk + S - 1) / S;
-    const int Se = (nk + kts - 1) / kts;  // slices that own at least one k-tile
-    gemm_nt_bf16_launch<64, 64>(kv, dim3(g64.x, g64.y, Se), st, x, w, nullptr, nullptr, (float*)workspace, M, N, K, 0,
-                                kts);
-    const long long MN = (long long)M * N;
-    long long grid = (MN + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)grid), dim3(256), 0, st, (const float*)workspace, b,
-                       res, y, MN, N, Se, act);
-  } else {
-    gemm_nt_bf16_launch<64, 64>(kv, g64, st, x, w, b, res, y, M, N, K, act, 0);
-  }
-  VS_CHECK_LAUNCH();
-  return VS_OK;
-}
 
 // ----------------------------------------------------------------------------
 // h[r, l, :] = wte[tok[r, l]] + wpe[pos0 + l]      (GPT2Model: default position ids)

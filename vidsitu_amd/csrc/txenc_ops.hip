@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void linear_fwd_kernel(const float* __restrict
         s += bias;
         if (act == 1) s = fmaxf(s, 0.f);
         else if (act == 2)  // transformers gelu_new
-          s = 0.5f * s * (1.0f + tanhf(0.7978845608028654f * (s + 0.044715f * s * s * s)));
+          s = gelu_new_f(s);
         if (res) s += res[(long long)(mbase + m) * N + n];
         y[(long long)(mbase + m) * N + n] = s;
       }
@@ -204,7 +204,7 @@ __device__ __forceinline__ void linear_fullx_body(const float* __restrict__ x, c
     for (int j = 0; j < 64; ++j) s += row[j];
     s += b ? b[n] : 0.f;
     if (act == 1) s = fmaxf(s, 0.f);
-    else if (act == 2) s = 0.5f * s * (1.0f + tanhf(0.7978845608028654f * (s + 0.044715f * s * s * s)));
+    else if (act == 2) s = gelu_new_f(s);
     if (res) s += res[(long long)lane * N + n];
     y[(long long)lane * N + n] = s;
   }
@@ -314,7 +314,7 @@ __global__ __launch_bounds__(256) void linear_rows16_kernel(const float* __restr
     if (n < N && m0 + m < M) {
       s += b ? b[n] : 0.f;
       if (act == 1) s = fmaxf(s, 0.f);
-      else if (act == 2) s = 0.5f * s * (1.0f + tanhf(0.7978845608028654f * (s + 0.044715f * s * s * s)));
+      else if (act == 2) s = gelu_new_f(s);
       if (res) s += res[(long long)(m0 + m) * N + n];
       y[(long long)(m0 + m) * N + n] = s;
     }
@@ -456,7 +456,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void linear_skinny_kernel
       if (m < M) {
         float sv = v[e] + bias;
         if (act == 1) sv = fmaxf(sv, 0.f);
-        else if (act == 2) sv = 0.5f * sv * (1.0f + tanhf(0.7978845608028654f * (sv + 0.044715f * sv * sv * sv)));
+        else if (act == 2) sv = gelu_new_f(sv);
         if (res) sv += res[(long long)m * N + n];
         if (ypk) y[(((long long)(m >> 4) * (N >> 4) + (n >> 4)) * 64 + ((n & 15) >> 2) * 16 + (m & 15)) * 4 + (n & 3)] = sv;
         else y[(long long)m * N + n] = sv;
@@ -600,9 +600,6 @@ extern "C" int vs_linear_fwd(const float* x, const float* w, const float* b, flo
 
 // y = act(x . w^T + b) + res, act 0 none / 1 relu / 2 gelu_new.  Up to 64 rows every weight row is
 // streamed exactly once by one wave (HBM-bound decode steps); above that the fp32 matrix cores.
-int vs_gemm_nt_f32_mfma(const float* x, const float* w, const float* b, const float* res, float* y,
-                        int M, int N, int K, int act, hipStream_t st, void* ws = nullptr, size_t ws_bytes = 0);
-
 extern "C" int vs_gemm_nt_f32(const float* x, const float* w, const float* b, const float* res,
                               float* y, int M, int N, int K, int act, void* stream) {
   VS_CHECK_ARG(x && w && y && M > 0 && N > 0 && K > 0, "bad args");

@@ -1178,20 +1178,13 @@ def gemm_nt(x, w, b=None, res=None, act=ACT_NONE, out=None, bf16=False):
     if w.shape[1] != k:
         raise _lib.VsError(f"gemm_nt: K mismatch {tuple(x.shape)} x {tuple(w.shape)}")
     y = torch.empty((m, n), dtype=torch.float32, device=x.device) if out is None else out
-    if bf16:
-        need = _lib.load().vs_gemm_nt_bf16_workspace_bytes(m, n, k)
-        ws = _workspace(need, x.device) if need else None
-        _lib.call("vs_gemm_nt_bf16_ws", _ptr(x), _ptr(w), _ptr(b), _ptr(res), _ptr(y), m, n, k, int(act),
-                  _ptr(ws), C.c_size_t(ws.numel() if need else 0), _stream())
-        return y
-    need = _lib.load().vs_gemm_nt_f32_workspace_bytes(m, n, k) if m > 64 else 0
-    if need:
-        ws = _workspace(need, x.device)
-        _lib.call("vs_gemm_nt_f32_ws", _ptr(x), _ptr(w), _ptr(b), _ptr(res), _ptr(y), m, n, k, int(act),
-                  _ptr(ws), C.c_size_t(ws.numel()), _stream())
-    else:
-        _lib.call("vs_gemm_nt_f32", _ptr(x), _ptr(w), _ptr(b), _ptr(res), _ptr(y), m, n, k, int(act),
-                  _stream())
+    size_fn, entry = (("vs_gemm_nt_bf16_workspace_bytes", "vs_gemm_nt_bf16_ws") if bf16 else
+                      ("vs_gemm_nt_f32_workspace_bytes", "vs_gemm_nt_f32_ws"))
+    need = getattr(_lib.load(), size_fn)(m, n, k)
+    ws = _workspace(need, x.device) if need else None
+    # without a workspace (and up to 64 rows) the fp32 entry is vs_gemm_nt_f32
+    _lib.call(entry, _ptr(x), _ptr(w), _ptr(b), _ptr(res), _ptr(y), m, n, k, int(act), _ptr(ws),
+              C.c_size_t(ws.numel() if need else 0), _stream())
     return y
 
 

@@ -84,6 +84,11 @@ typedef struct vs_conv_desc {
 
 const char* vs_last_error_string(void);
 int vs_version(void);
+/* The value the library resolved for one of the environment switches it reads ("Environment
+ * switches"; the table is csrc/switches.h), by full name such as "VS_CONV_DEEP": the variable's value if it was set
+ * when the switch was first asked for, else the default.  Read-only -- there is no setter.  Needs no GPU.
+ * VS_ERR_BAD_ARG for a name the library does not read or a null pointer. */
+int vs_switch_value(const char* name, double* value);
 /* Kernel launches issued by this library so far (process-wide, relaxed atomic; every launch site counts).
  * bench.py reports launches per step from it -- the reference's step is a chain of cuDNN / ATen launches
  * (utils/trn_utils.py:590-615), the length of that chain is what bounds the batch-8 step here. */

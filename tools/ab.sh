@@ -390,16 +390,6 @@ for il in 0 2; do
   echo "== tile kernel only (--nohalo --nodeep), VS_CONV_SPLITK_IL=$il"; tail -32 $OUT/tile_il$il.txt | cut -c1-120
 done
 ;;
-r4_wgrad_align_probe)
-# Round-4: (1) deep weight-gradient kernel with whole splits per XCD (VS_WGRAD_DEEP_ALIGN=1) vs not, 32 and 8 clips;
-# (2) the GEMM probe's staggered all-wave copy issue against halves-burst.
-export TMPDIR=/tmp
-OUT=gpurun_out/r4_wgrad_align; mkdir -p $OUT
-for c in 32 8; do for al in 1 0; do
-  VS_WGRAD_DEEP_ALIGN=$al timeout 900 python tools/fwd_layer_times.py wgrad --clips=$c --only=s3.p0,s4.p0,s5.p0 --deep > $OUT/wgrad_${c}_align$al.txt 2>&1; echo "clips $c align $al: $(tail -1 $OUT/wgrad_${c}_align$al.txt)"
-done; done
-timeout 600 tools/probes/gemm_deep > $OUT/gemm_deep_v4.txt 2>&1; echo "probe exit $?"; cut -c1-250 $OUT/gemm_deep_v4.txt | grep -v check
-;;
 r4_wgrad_deep)
 # Round-4: the deep-pipeline weight-gradient kernel -- parity tests, per-layer table forced / plan / off at 8 and 32 clips,
 # the train step with the plan on / off (VS_WGRAD_DEEP=1 / 0).
@@ -426,16 +416,6 @@ for a in 1 0; do
   VS_WGRAD_DEEP=$a timeout 600 python bench.py --clips-per-gpu 32 --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-feat-fwd 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('train 32 clips wgrad_deep $a', d['value'], d['ms_per_step'])"
 done
 ;;
-r4_wgrad_half)
-# Round-4: weight-gradient ring kernel with half stages (4 x 32 positions in 64 KiB, 3 steps in flight; VS_WGRAD_HALF=1)
-# against the two-stage ring: parity tests with it on, per-layer table, 8 clips.
-export TMPDIR=/tmp
-OUT=gpurun_out/r4_wgrad_half; mkdir -p $OUT
-VS_WGRAD_HALF=1 timeout 900 python -m pytest tests/test_gpu_conv.py -q -m gpu -x -k "wgrad" --no-header -p no:cacheprovider > $OUT/pytest.log 2>&1; echo "pytest half exit $?"; tail -3 $OUT/pytest.log
-for h in 1 0 1 0; do
-  VS_WGRAD_HALF=$h timeout 900 python tools/fwd_layer_times.py wgrad > $OUT/wgrad_8_half${h}_$RANDOM.txt 2>&1; echo "half $h: $(tail -1 $(ls -t $OUT/wgrad_8_half${h}_*.txt | head -1))"
-done
-;;
 r4_wgrad_stag)
 # Round-4: deep weight-gradient kernel, staggered all-wave copy issue (VS_WGRAD_DEEP_STAG=1) against the halves issue.
 export TMPDIR=/tmp
@@ -453,21 +433,6 @@ for rep in 1 2; do for w in 0 4; do
   VS_WHATIF_OK=1 VS_WHATIF=$w timeout 600 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-roofline --no-feat-fwd 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('train whatif $w', d['value'], d['ms_per_step'])"
 done; done
 ;;
-r4_wgrad_xcd)
-# Round-4: weight gradients with one position split per XCD (S a multiple of 8 + XCD-contiguous block order) against
-# the round-3 split choice (VS_WGRAD_ALIGN8=0), per layer and in the step; then the train step's timeline.
-export TMPDIR=/tmp
-OUT=gpurun_out/r4_wgrad_xcd; mkdir -p $OUT
-timeout 900 python -m pytest tests/test_gpu_conv.py -q -m gpu -x -k "wgrad" --no-header -p no:cacheprovider > $OUT/pytest_wgrad.log 2>&1; echo "pytest wgrad exit $?"; tail -3 $OUT/pytest_wgrad.log
-for a in 1 0; do
-  VS_WGRAD_ALIGN8=$a timeout 900 python tools/fwd_layer_times.py wgrad > $OUT/wgrad_8_align$a.txt 2>&1; echo "wgrad table align $a exit $?"; tail -1 $OUT/wgrad_8_align$a.txt
-done
-VS_WGRAD_ALIGN8=1 VS_WGRAD_XCD=2 timeout 900 python tools/fwd_layer_times.py wgrad > $OUT/wgrad_8_align1_xcd2.txt 2>&1; tail -1 $OUT/wgrad_8_align1_xcd2.txt
-for rep in 1 2 3; do for a in 1 0; do
-  VS_WGRAD_ALIGN8=$a timeout 600 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-roofline --no-feat-fwd 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('train align8 $a', d['value'], d['ms_per_step'])"
-done; done
-bash tools/timeline.sh sf_txenc_train > $OUT/timeline_train.txt 2>&1; tail -70 $OUT/timeline_train.txt
-;;
 r4_whatif)
 # Round-4 what-if table: the replayed train step with whole kernel families skipped (VS_WHATIF bits: 1 bn_finalize, 2 bn_bwd_finalize,
 # 4 conv_wgrad + slab reduce, 8 bn_apply / bn_bwd_reduce / bn_bwd_apply).  Garbage numerics: timing only.
@@ -477,6 +442,6 @@ for rep in 1 2; do for w in 0 4 8 11 15; do
 done; done
 ;;
 *)
-echo "usage: tools/ab.sh <experiment> [args]; experiments: r5_final r2_final r3_ab_noslp r3_ab_wgrad_unsplit r3_batch_probe r3_batch_probe_large r3_final r3_parity r4_ab_deep r4_ab_lib r4_baseline_tables r4_batch_probe r4_bnred_ab r4_check r4_deep_first r4_direct_tpw r4_final r4_halo_pmc r4_knob_sweep r4_korder_timeline r4_kstats r4_kstats32 r4_nt_ab r4_plan_ab r4_reduce_ab r4_splitk_il r4_wgrad_align_probe r4_wgrad_deep r4_wgrad_deep_step r4_wgrad_half r4_wgrad_stag r4_wgrad_whatif r4_wgrad_xcd r4_whatif"; exit 2
+echo "usage: tools/ab.sh <experiment> [args]; experiments: r5_final r2_final r3_ab_noslp r3_ab_wgrad_unsplit r3_batch_probe r3_batch_probe_large r3_final r3_parity r4_ab_deep r4_ab_lib r4_baseline_tables r4_batch_probe r4_bnred_ab r4_check r4_deep_first r4_direct_tpw r4_final r4_halo_pmc r4_knob_sweep r4_korder_timeline r4_kstats r4_kstats32 r4_nt_ab r4_plan_ab r4_reduce_ab r4_splitk_il r4_wgrad_deep r4_wgrad_deep_step r4_wgrad_stag r4_wgrad_whatif r4_whatif"; exit 2
 ;;
 esac

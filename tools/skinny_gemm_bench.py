@@ -1,6 +1,6 @@
 """Decode-step GEMMs of GPT-2 medium at M rows (default 50 = 10 sentences x beam 5): time per call,
 weight-streaming rate and fp32 MFMA rate (eager launches: run under rocprofv3 --kernel-trace for
-kernel times, tools/skinny_prof.sh)."""
+kernel times)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -7,9 +7,11 @@ import ctypes as C
 import os
 import subprocess
 
+from . import switches
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VS_LIB_PATH: A/B runs of two builds of the same ABI in one GPU session (tools/); never a fallback.
-LIB_PATH = os.environ.get("VS_LIB_PATH") or os.path.join(_HERE, "libvidsitu_hip.so")
+LIB_PATH = switches.read("VS_LIB_PATH") or os.path.join(_HERE, "libvidsitu_hip.so")
 CSRC_DIR = os.path.join(_HERE, "csrc")
 
 VS_CONV_AFFINE = 1
@@ -78,6 +80,7 @@ _dp = C.POINTER(ConvDesc)
 SIGNATURES = {
     "vs_last_error_string": (C.c_char_p, []),
     "vs_version": (_i, []),
+    "vs_switch_value": (_i, [C.c_char_p, C.POINTER(_d)]),
     "vs_launch_count": (_i64, []),
     "vs_pack_input": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
     "vs_frames_u8_pack": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p]),

@@ -16,6 +16,8 @@ import os
 
 import torch
 
+from . import switches
+
 
 def _strip_module(sd):
     if sd and all(k.split(".")[0] == "module" for k in sd):
@@ -75,7 +77,7 @@ def load_model_dict(path, mdl, optimizer=None, load_opt=False, strict=True, aren
         try:
             ckpt = torch.load(f, map_location="cpu", weights_only=True)
         except pickle.UnpicklingError as e:
-            if os.environ.get("VS_CKPT_UNSAFE_LOAD") != "1":
+            if switches.read("VS_CKPT_UNSAFE_LOAD") != "1":
                 raise RuntimeError(
                     f"{path}: the checkpoint holds objects the safe (weights_only) loader refuses -- typically a numpy "
                     f"scalar in `best_met` written by the reference trainer.  If the file is trusted, set "

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 #include "glue_bodies.h"
 
 // ----------------------------------------------------------------------------
@@ -448,7 +449,7 @@ __global__ __launch_bounds__(1024) void bn_finalize2_wgrad_reduce_kernel(Fin2P f
 
 // groups of the plan: one up to 256 rows (every slice-thread's rows in ONE batch of 8), else groups of 256 rows, at most 32
 static bool fin2_plan(Fin2P& f, int nparts, int C, void* ws, size_t ws_bytes) {
-  static const int on = [] { const char* e = getenv("VS_BN_FIN2"); return e ? atoi(e) : 1; }();
+  const int on = vs_sw::env_BN_FIN2();
   if (!on || ws == nullptr || ws_bytes < vs_bn_finalize_workspace_bytes() || C > 4096) return false;
   int rpg = 256;
   while ((nparts + rpg - 1) / rpg > 32) rpg += 256;
@@ -588,8 +589,7 @@ __device__ __forceinline__ uint4 ld_stream16(const uint16_t* p) {
 
 static int bn_rows_batches(long long rows, int C, int target_blocks) {
   // VS_BN_TARGET / VS_BN_NBMAX: sweep knobs (tools/bn_time.py); the defaults are what the sweep kept
-  static const int env_target = getenv("VS_BN_TARGET") ? atoi(getenv("VS_BN_TARGET")) : 0;
-  static const int env_nbmax = getenv("VS_BN_NBMAX") ? atoi(getenv("VS_BN_NBMAX")) : 0;
+  const int env_target = vs_sw::env_BN_TARGET(), env_nbmax = vs_sw::env_BN_NBMAX();
   if (env_target > 0) target_blocks = env_target;
   const int nbmax = env_nbmax > 0 ? env_nbmax : 4;
   const int cpr = C / 8;

@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "conv_tile.h"
+#include "switches.h"
 
 #define DEEP_EP 260  // fp32 epilogue row pitch (floats): lane quarters 4 rows apart land 16 banks apart
 
@@ -466,7 +467,7 @@ __global__ __launch_bounds__(512) void conv_deep_kernel(ConvP p) {
 
 // ------------------------------ host side ------------------------------------
 static int deep_mode() {
-  static const int on = [] { const char* e = getenv("VS_CONV_DEEP"); return e ? atoi(e) : 1; }();
+  const int on = vs_sw::env_CONV_DEEP();
   return on;
 }
 

@@ -25,6 +25,7 @@
 #include <stdlib.h>
 
 #include "conv_tile.h"
+#include "switches.h"
 
 #define HALO_RA_MAX 352  // image rows per tile (x 128 B per 64-channel chunk)
 #define HALO_LA (HALO_RA_MAX / 32)
@@ -375,7 +376,7 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(ConvP p, HaloGeo q) {
 
 // ------------------------------ host side ------------------------------------
 static int halo_enabled() {
-  static const int on = [] { const char* e = getenv("VS_CONV_HALO"); return e ? atoi(e) : 1; }();
+  const int on = vs_sw::env_CONV_HALO();
   return on;
 }
 
@@ -454,7 +455,7 @@ bool vs_halo_plan(const ConvP& p, int mode, int dgrad, int flags, HaloGeo* out) 
         // serves a ds_read_b128 in lane groups that MIX two k-units, and an odd tap shift or a line wrap puts two of
         // a group's rows on one slot -- tools/probes/halo_lds_sim.py).  VS_HALO_CONFLICT_WEIGHT: A/B of the planner's
         // price for it (lower = prefer the padded lines).
-        static const double cw = [] { const char* e = getenv("VS_HALO_CONFLICT_WEIGHT"); return e ? atof(e) : 0.85; }();
+        const double cw = vs_sw::env_HALO_CONFLICT_WEIGHT();
         const double conflicts = (!temporal && !pad && (W % 16) != 0) ? cw : 1.0;
         const double score = eff * fill * conflicts * (inten > 96.0 ? 1.0 : 0.6 + 0.4 * inten / 96.0) * (1.0 + 1e-4 * inten);
         if (score > best_score) { best_score = score; best = g; }

@@ -16,6 +16,7 @@
 // 128-byte LDS rows (conflict-free ds_read_b128 fragment reads), fp32 epilogue
 // staged through LDS so stores are whole 16-byte channel vectors.
 #include "common.h"
+#include "switches.h"
 
 #include <mutex>
 
@@ -1075,7 +1076,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(ConvP p, int tiles_per
 // (0.316 vs 0.317 ms forward, 200 704-row layers with 784 instead of 392 blocks), 10 % slower at 1024, and 0.4 % slower
 // in the step (more BN partial rows): off by default (profiles/r04_direct_tpw.txt).
 static int direct_tpw(long long M) {
-  static const long long want = [] { const char* e = getenv("VS_DIRECT_TPW_BLOCKS"); return e ? atoll(e) : 0ll; }();
+  const long long want = vs_sw::env_DIRECT_TPW_BLOCKS();
   int tpw = 8;
   while (want > 0 && tpw > 2 && (M + 64 * tpw - 1) / (64 * tpw) < want) tpw >>= 1;
   return tpw;
@@ -1102,10 +1103,7 @@ static int launch_direct_tb(const ConvP& p, int mode, hipStream_t st) {
 
 // tiles in flight per wave: VS_DIRECT_TB=1|2|4 overrides the rule (A/B runs)
 static int direct_tb(int nt, int ks) {
-  static const int forced = [] {
-    const char* e = getenv("VS_DIRECT_TB");
-    return e ? atoi(e) : 0;
-  }();
+  const int forced = vs_sw::env_DIRECT_TB();
   if (forced == 1 || forced == 2 || forced == 4) return forced;
   return (nt * ks <= 6) ? 4 : 2;
 }
@@ -1327,11 +1325,7 @@ static int launch_direct_bc_ks(const ConvP& p, const BcP& q, hipStream_t st) {
 // 32 inner channels, 9 taps (fast res4: K = 288 = 9 k-steps, 72 weight registers per lane): two tiles in flight,
 // fewer tiles per wave than the 8 / 16-channel layers (a quarter of their rows)
 static int launch_direct_bc32(const ConvP& p, const BcP& q, hipStream_t st) {
-  static const int tpw = [] {
-    const char* e = getenv("VS_BC32_TPW");
-    const int v = e ? atoi(e) : 4;
-    return v < 2 ? 2 : (v & ~1);
-  }();
+  const int v = vs_sw::env_BC32_TPW(), tpw = v < 2 ? 2 : (v & ~1);
   const int grid = (int)((p.M + 64ll * tpw - 1) / (64ll * tpw));
   hipLaunchKernelGGL((conv_direct_bc_kernel<2, 9, 1, 2, 8>), dim3(grid), dim3(256), 0, st, p, q, tpw);
   VS_CHECK_LAUNCH();
@@ -1557,10 +1551,7 @@ struct ConvPlan {
 // (profiles/r04_splitk_in_launch.txt) it loses on every layer of the step -- a 128 x 128 fp32 partial is 64 KiB written
 // through and read back per block, the operand traffic of four k-steps, and the layers it would fill the chip for are
 // already on the halo-image / deep kernels.
-static int splitk_il_mode() {
-  static const int m = [] { const char* e = getenv("VS_CONV_SPLITK_IL"); return e ? atoi(e) : 0; }();
-  return m;
-}
+static int splitk_il_mode() { return vs_sw::env_CONV_SPLITK_IL(); }
 
 // Few-tile, deep-K layers (slow s4 / s5 at batch 8: 100-400 tiles for 256 CUs) leave each CU
 // with at most one block, which is bound by bytes-in-flight / latency; splitting K puts 2-4
@@ -1594,8 +1585,7 @@ static ConvPlan plan_conv(long long M, int Ncols, int K, int taps, int flags) {
   // CU; the tile's last arriver sums the S partial accumulators in split order and runs the ordinary epilogue.
   {
     const int il = (flags & VS_CONV_NOSPLITK_IL) ? 0 : ((flags & VS_CONV_SPLITK_IL) ? 2 : splitk_il_mode());
-    static const int il_tiles = [] { const char* e = getenv("VS_CONV_SPLITK_IL_TILES"); return e ? atoi(e) : 224; }();
-    static const int il_nk = [] { const char* e = getenv("VS_CONV_SPLITK_IL_NK"); return e ? atoi(e) : 32; }();
+    const int il_tiles = vs_sw::env_CONV_SPLITK_IL_TILES(), il_nk = vs_sw::env_CONV_SPLITK_IL_NK();
     const bool shape_ok = Ncols >= 128 && Ncols % 8 == 0 && taps <= 31 && nk >= 8 && fring == 0 && forced == 0;
     if (il && shape_ok && !(flags & VS_CONV_SPLITK) && (il == 2 || (t128 <= il_tiles && nk >= il_nk))) {
       long long S = (512 + t128 / 2) / t128;  // ~2 blocks per CU
@@ -1736,7 +1726,7 @@ static ConvChoice choose_conv(const ConvP& p, int mode, int flags, ConvState s) 
 static int launch_conv(ConvP& p, int mode, int flags, void* ws, size_t ws_bytes, hipStream_t st) {
   {
     // chunk-major reduction (ConvP::korder) where a tap spans at least VS_CONV_KORDER_MIN k-tiles (default 2; 0 = never)
-    static const int kmin = [] { const char* e = getenv("VS_CONV_KORDER_MIN"); return e ? atoi(e) : 2; }();
+    const int kmin = vs_sw::env_CONV_KORDER_MIN();
     const int taps = p.kT * p.kH * p.kW;
     p.korder = (kmin > 0 && mode != 0 && taps > 1 && taps <= 31 && p.Cg % 64 == 0 && p.Cg / 64 >= kmin) ? 1 : 0;
   }
@@ -2113,7 +2103,7 @@ extern "C" int vs_conv_dgrad_bnstats_rows(const vs_conv_desc* d) {
     // issue, not by bandwidth: with the mask / sum arithmetic in its copy-out the step is 0.1-0.2 ms SLOWER
     // than the plain launch plus the separate (bandwidth-bound) reduce pass -- 13.05 / 13.19 vs 12.83 / 13.08 ms,
     // A/B on one box.  Opt-in: VS_CONV_DIRECTBNB in desc.flags, or VS_DIRECT_BNB=1.
-    static const int on = [] { const char* e = getenv("VS_DIRECT_BNB"); return e ? atoi(e) : 0; }();
+    const int on = vs_sw::env_DIRECT_BNB();
     return (on || (d->flags & VS_CONV_DIRECTBNB)) ? c.tilesM : 0;
   }
   if (c.kind == CONV_HALO || c.kind == CONV_PW || c.kind == CONV_DEEP) return c.tilesM;

@@ -17,6 +17,7 @@
 // The epilogue is conv_tile_epilogue (conv_tile.h): batch-statistic partials, folded-BN affine, masked
 // residual, ReLU, and -- BNB -- the consumer unit's BN-backward sums, bitwise the tile kernel's results.
 #include "common.h"
+#include "switches.h"
 
 #include "conv_tile.h"
 
@@ -220,14 +221,8 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(ConvP p, PwGeo g) {
 }
 
 // ------------------------------ host side ------------------------------------
-static int pw_env(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-
 bool vs_pw_plan(const ConvP& p, int mode, int flags, bool bnb, PwGeo* out) {
-  static const int on = pw_env("VS_CONV_PW", 1), f_bn = pw_env("VS_PW_BN", 0), f_ns = pw_env("VS_PW_NSLOT", 0),
-                   f_occ = pw_env("VS_PW_OCC", 0);
+  const int on = vs_sw::env_CONV_PW(), f_bn = vs_sw::env_PW_BN(), f_ns = vs_sw::env_PW_NSLOT(), f_occ = vs_sw::env_PW_OCC();
   if (!on || mode != 0 || (flags & VS_CONV_NOPW)) return false;
   if (((flags >> 8) & 0xf) || ((flags >> 16) & 7) || (flags & (VS_CONV_SPLITK | (7 << 12)))) return false;  // forced plans / debug
   if (p.kT * p.kH * p.kW != 1 || p.K > 512 || p.K % 8 || p.Ncols < 64 || p.Ncols % 8 || p.M < 2048) return false;
@@ -266,7 +261,7 @@ bool vs_pw_plan(const ConvP& p, int mode, int flags, bool bnb, PwGeo* out) {
   if (8 * gx > g.tilesM) gx = (g.tilesM + 7) / 8;
   g.gx = gx;
   g.ngroups = 8 * gx;
-  g.dbg = pw_env("VS_PW_DBG", 0);
+  g.dbg = vs_sw::env_PW_DBG();
   g.dense = (p.mulT == 1 && p.mulH == 1 && p.mulW == 1 && p.Gt == p.Rt && p.Gh == p.Rh && p.Gw == p.Rw) ? 1 : 0;
   *out = g;
   return true;
@@ -296,7 +291,7 @@ static int pw_launch_edbg(const ConvP& p, const PwGeo& g, hipStream_t st) {
 
 int vs_pw_launch(const ConvP& p, const PwGeo& g, hipStream_t st) {
   const bool bnb = (p.flags & VS_CONV_BNBWD) != 0;
-  static const int edbg = pw_env("VS_PW_EDBG", 0);  // epilogue ablations (tools only): 1 no statistics, 2 no staging writes
+  const int edbg = vs_sw::env_PW_EDBG();  // epilogue ablations (tools only): 1 no statistics, 2 no staging writes
   if (edbg && g.bn == 128 && !bnb) {
     if (edbg == 1) return pw_launch_edbg<1>(p, g, st);
     if (edbg == 2) return pw_launch_edbg<2>(p, g, st);

@@ -10,6 +10,7 @@
 // aligned because 2*wo + dw0 is even), B fragments come from the whole packed weight
 // [Cout][kT][7][8][4], resident in LDS across a persistent loop over tiles.
 #include "common.h"
+#include "switches.h"
 
 #define ST_TH 8
 #define ST_TW 16
@@ -635,7 +636,7 @@ extern "C" int vs_stem_conv_fwd(const void* x4, const void* wp, void* y, int N, 
   p.ntiles = N * p.tilesH * p.tilesW * p.tchunks;
   const int CP = (Cout + 15) / 16 * 16;
   hipStream_t st = (hipStream_t)stream;
-  static const int pair_on = [] { const char* e = getenv("VS_STEM_PAIR"); return e ? atoi(e) : 1; }();
+  const int pair_on = vs_sw::env_STEM_PAIR();
   if (pair_on == 1 && Cout == 8 && kT >= 3 && T >= 2) {  // two output frames per pass, weights in registers
     p.tchunks = (T + SP_TC - 1) / SP_TC;
     p.ntiles = N * p.tilesH * p.tilesW * p.tchunks;
@@ -995,7 +996,7 @@ __global__ __launch_bounds__(256) void stem_slab_reduce_kernel(const float* slab
 static int stem_wg_grid(int nitems) { return nitems < 512 ? nitems : 512; }
 
 static bool stem_wg_pair(int T, int Cout, int kT) {
-  static const int on = [] { const char* e = getenv("VS_STEM_PAIR"); return e ? atoi(e) : 1; }();
+  const int on = vs_sw::env_STEM_PAIR();
   return on && Cout == 8 && (kT == 3 || kT == 5) && T >= 2;
 }
 

@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 
 #include <mutex>
 #include <type_traits>
@@ -1099,7 +1100,7 @@ struct WgCfg {
 // is one residency round.  Where it pays (profiles/r04_wgrad_deep.txt): >= 128 output channels and >= 192 columns
 // mostly filling their tiles, enough tiles x splits for >= half the chip, >= 16 units of 32 positions per block.
 static bool wg_deep_plan(const vs_conv_desc* d, WgCfg* c) {
-  static const int mode = [] { const char* e = getenv("VS_WGRAD_DEEP"); return e ? atoi(e) : 1; }();
+  const int mode = vs_sw::env_WGRAD_DEEP();
   const bool force = mode == 2 || (d->flags & VS_WGRAD_FORCEDEEP);
   if (mode == 0 || (d->flags & VS_WGRAD_NODEEP)) return false;
   if (((d->flags >> 8) & 0xf) || ((d->flags >> 16) & 7) || ((d->flags >> 24) & 0xff)) return false;  // forced tile / ring / slots
@@ -1127,7 +1128,7 @@ static bool wg_deep_plan(const vs_conv_desc* d, WgCfg* c) {
   // data gradient without accumulator moves) the same A/B reads +0.5-0.7 % with them on the deep kernel (floor 10 000:
   // 668.3-669.9 vs 662.1-666.5 clips/s; floor 3 000: another +0.2 %; 0 = 3 000; VS_WGRAD_DEEP=2 everywhere: -2.7 %;
   // profiles/r04_wgrad_deep_floor.txt).  From 32 clips on the step gains 2.5 %.
-  static const long long min_p = [] { const char* e = getenv("VS_WGRAD_DEEP_MINP"); return e ? atoll(e) : 3000ll; }();
+  const long long min_p = vs_sw::env_WGRAD_DEEP_MINP();
   if (!force && P < min_p) return false;
   if (tiles * S > 65535) return false;
   c->bm = 128;
@@ -1175,14 +1176,8 @@ static WgCfg wg_pick(const vs_conv_desc* d) {
   // stand-alone speed (256 costs the kernel alone 13 %).
   // Skinny outputs (fast pathway: a handful of tiles, 10^5..10^6 positions) get one residency round too: 512
   // blocks (2048, several rounds of short blocks, was 25-50 % slower; 256 / 384 / 768 slower as well).
-  static const long long slots = [] {
-    const char* e = getenv("VS_WGRAD_SLOTS");  // experiment knob: resident block slots to fill
-    return e ? atoll(e) : 384ll;
-  }();
-  static const long long small_slots = [] {
-    const char* e = getenv("VS_WGRAD_SLOTS_SMALL");
-    return e ? atoll(e) : 512ll;
-  }();
+  const long long slots = vs_sw::env_WGRAD_SLOTS();  // experiment knob: resident block slots to fill
+  const long long small_slots = vs_sw::env_WGRAD_SLOTS_SMALL();
   long long target = (d->Cout <= 32) ? small_slots : slots;
   const int forced_slots = (d->flags >> 24) & 0xff;  // experiments: resident block slots / 8 in bits 24..31
   if (forced_slots) target = 8ll * forced_slots;
@@ -1194,10 +1189,7 @@ static WgCfg wg_pick(const vs_conv_desc* d) {
   // dgrad's tiles in the same grid (conv_pair.hip) the chip is full either way.  Train step 12.311-12.314 ms against
   // 12.321-12.361 (alternating, one box: profiles/r03_wgrad_unsplit.txt); a threshold of 96 tiles is slower (12.43).
   // VS_WGRAD_S1_TILES overrides (0 = never).
-  static const long long s1_tiles = [] {
-    const char* e = getenv("VS_WGRAD_S1_TILES");
-    return e ? atoll(e) : 128ll;
-  }();
+  const long long s1_tiles = vs_sw::env_WGRAD_S1_TILES();
   if (s1_tiles > 0 && tiles >= s1_tiles && !forced_slots) S = 1;
   const long long maxS = (P + 511) / 512;
   if (S > maxS) S = maxS;
@@ -1333,7 +1325,7 @@ static bool wgg_item_ok(const vs_conv_desc* d) {
 #define WGG_C0 14
 static bool wgg_plan(const vs_wgrad_item* it, int n, WgCfg* cfg, size_t* slab_off, size_t* slab_total, int* order) {
   if (n < 1 || n > WGG_MAX) return false;
-  static const int slots = [] { const char* e = getenv("VS_WGG_SLOTS"); const int v = e ? atoi(e) : 256; return v < 1 ? 1 : (v > 1024 ? 1024 : v); }();
+  const int v = vs_sw::env_WGG_SLOTS(), slots = v < 1 ? 1 : (v > 1024 ? 1024 : v);
   long long units[WGG_MAX], P[WGG_MAX], maxS[WGG_MAX], dwn[WGG_MAX];
   int tiles[WGG_MAX];
   long long W = 0, umax = 0;
@@ -1511,7 +1503,7 @@ extern "C" int vs_conv_wgrad_group(const vs_wgrad_item* items, int n, void* work
     // Default OFF: measured (profiles/r06_wgrad_jobs.txt) the mapping halves the launch's fabric-side bytes (443 -> 220 MB,
     // L2 hit rate 0.30 -> 0.63) and buys no time -- neutral alone, 0.8 % SLOWER in the step: the deep body is bound by
     // its LDS-DMA issue, not by where its operands come from.  VS_WGG_JOBS=1: on.
-    static const int jobs_on = [] { const char* e = getenv("VS_WGG_JOBS"); return e ? atoi(e) : 0; }();
+    const int jobs_on = vs_sw::env_WGG_JOBS();
     bool fits = jobs_on != 0 && n <= 32;
     int cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int x = 0; x < 8; ++x) {
@@ -1590,13 +1582,12 @@ static int wgrad_impl(const void* dy, const void* x, float* dw, const vs_conv_de
     if (rc) return rc;
   }
   {
-    static const int xo = [] { const char* e = getenv("VS_WGRAD_XCD"); return e ? atoi(e) : 1; }();
+    const int xo = vs_sw::env_WGRAD_XCD();
     // measured per layer (batch 8): a win up to ~16 output tiles (s3.b 43.5 -> 35.4 us, s4.c 22.1 -> 19.7,
     // s3.c 24.7 -> 21.2, s2.c 29.7 -> 26.4), a loss from 36 tiles on (s4.b 36.7 -> 38.9, s5.b 48.9 -> 52.9), where
     // one split's tiles no longer fit an XCD's share of the grid anyway
     p.xcd_order = xo && (c.tilesM * c.tilesN <= 32 || xo == 2 || (c.S % 8 == 0 && c.tilesM * c.tilesN <= 64));
-    static const int dbg = [] { const char* e = getenv("VS_WGRAD_DBG"); return e ? atoi(e) : 0; }();
-    p.dbg = dbg;
+    p.dbg = vs_sw::env_WGRAD_DBG();
   }
   p.rows_per_split = c.rows_per_split;
   const bool dense = (d->kT * d->kH * d->kW == 1) && d->sT == 1 && d->sH == 1 && d->sW == 1 &&
@@ -1618,7 +1609,7 @@ static int wgrad_impl(const void* dy, const void* x, float* dw, const vs_conv_de
       (void)hipFuncSetAttribute((const void*)conv_wgrad_deep_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       (void)hipFuncSetAttribute((const void*)conv_wgrad_deep_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
-    static const int stag = [] { const char* e = getenv("VS_WGRAD_DEEP_STAG"); return e ? atoi(e) : 1; }();  // +2.7 % at 32 clips, neutral at 8
+    const int stag = vs_sw::env_WGRAD_DEEP_STAG();  // +2.7 % at 32 clips, neutral at 8
     const size_t smem = (size_t)WGD_NU * WGD_UNIT + 2 * WGD_TAB * sizeof(int2);
     const int grid = p.tilesM * p.tilesN * p.S;
     if (stag && mode == 0) hipLaunchKernelGGL((conv_wgrad_deep_kernel<0, true>), dim3(grid), dim3(512), smem, st, p);

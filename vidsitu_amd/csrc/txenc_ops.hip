@@ -9,7 +9,10 @@
 // Everything here is weight-bandwidth / latency bound (M = 5*B <= 64 rows), so
 // it stays in exact fp32 on the VALU: each weight row is streamed once per
 // 64-row slab, activations are staged in LDS, reductions are wave shuffles.
+#include <string.h>
+
 #include "common.h"
+#include "switches.h"
 
 #include <mutex>
 
@@ -749,10 +752,7 @@ static void launch_bwd_fused(const float* dy, const float* relu_y, const float* 
   {
     // tools only (timing experiment, GARBAGE parameter gradients): what the weight-gradient half of these launches costs
     // the step -- the upper bound of moving it to a side stream.  Needs VS_WHATIF_OK=1 beside it.
-    static const int skip_dw = [] {
-      const char* e = getenv("VS_WHATIF_LINEAR_DW"); const char* ok = getenv("VS_WHATIF_OK");
-      return (e && atoi(e) && ok && atoi(ok)) ? 1 : 0; }();
-    if (skip_dw) g2 = 0;
+    if (vs_sw::env_WHATIF_LINEAR_DW() && vs_sw::env_WHATIF_OK()) g2 = 0;
   }
   hipLaunchKernelGGL((linear_bwd_fused_kernel<8, KC, VEC>), dim3((unsigned)(g1 + g2)), dim3(256), smem, st, dy,
                      relu_y, x, wt, dx, dw, db, M, N, K, g1, (int)g2, dx_res);
@@ -1338,7 +1338,7 @@ extern "C" int vs_add_layernorm_bwd(const float* dy, const float* x, const float
   VS_CHECK_ARG(D >= 1 && D <= 64 * LN_MAXE, "D <= 2048");
   const uintptr_t al = (uintptr_t)dy | (uintptr_t)x | (uintptr_t)r | (uintptr_t)rmask | (uintptr_t)gamma |
                        (uintptr_t)dx | (uintptr_t)dr;
-  static const int fuse = [] { const char* e = getenv("VS_LN_BWD_FUSED"); return e ? atoi(e) : 1; }();
+  const int fuse = vs_sw::env_LN_BWD_FUSED();
   if (fuse && (D & 3) == 0 && D <= 1024 && (al & 15) == 0 && rows <= 64) {
     const int g1 = (rows + 15) / 16;
     hipLaunchKernelGGL(add_layernorm_bwd_fused_kernel, dim3(g1 + (D + 63) / 64), dim3(1024), 0, (hipStream_t)stream,
@@ -1870,6 +1870,20 @@ void vs_set_error(const char* fmt, ...) {
 }
 extern "C" const char* vs_last_error_string(void) { return g_err; }
 extern "C" int vs_version(void) { return 1; }
+
+// what the library resolved a switch of switches.h to (read-only: there is no setter)
+extern "C" int vs_switch_value(const char* name, double* value) {
+  VS_CHECK_ARG(name && value, "null name or value");
+#define VS_SWITCH_ANSWER(n, type, dflt)   \
+  if (!strcmp(name, "VS_" #n)) {          \
+    *value = (double)vs_sw::env_##n();    \
+    return VS_OK;                         \
+  }
+  VS_SWITCHES(VS_SWITCH_ANSWER)
+#undef VS_SWITCH_ANSWER
+  vs_set_error("vs_switch_value: the library reads no switch named %s", name);
+  return VS_ERR_BAD_ARG;
+}
 
 #include <atomic>
 static std::atomic<long long> g_launches{0};

@@ -13,7 +13,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _lib, switches
 from ._lib import (  # noqa: F401  (re-exported flags)
     VS_CONV_AFFINE,
     VS_CONV_BNB2,
@@ -437,19 +437,14 @@ def conv_dgrad(dy, wt, xs, k, s, p, out=None, residual=None, naive=False, tile=N
 
 
 _ws_cache = {}
-import os as _os_wi
-# VS_WHATIF (tools/whatif.sh: whole kernel families skipped to time what they cost -- GARBAGE numerics) is refused unless
-# the tools-only guard VS_WHATIF_OK=1 stands beside it: a leaked variable must not train silently on garbage.
-if int(_os_wi.environ.get("VS_WHATIF", "0")) != 0 and _os_wi.environ.get("VS_WHATIF_OK") != "1":
-    raise RuntimeError("VS_WHATIF skips kernel launches (garbage numerics, timing experiments only): set VS_WHATIF_OK=1 "
-                       "beside it, or unset it")
-_WHATIF_WGRAD = (int(_os_wi.environ.get("VS_WHATIF", "0")) & 4) != 0  # tools only (see conv_wgrad)
+# tools only: skip launches to measure what they cost on the step (raises here unless VS_WHATIF_OK=1 stands beside it)
+_WHATIF = switches.read("VS_WHATIF")
+_WHATIF_WGRAD = (_WHATIF & 4) != 0  # (see conv_wgrad)
 
 
 # The slab reduce behind a weight gradient and the next unit's BN-backward finalize as ONE launch
 # (vs_wgrad_reduce_defer): VS_REDUCE_MERGE=0 switches it off (A/B; the results are bitwise the same).
-import os as _os_rm
-REDUCE_MERGE = _os_rm.environ.get("VS_REDUCE_MERGE", "1") != "0"
+REDUCE_MERGE = switches.read("VS_REDUCE_MERGE")
 
 
 def wgrad_reduce_defer(mode):
@@ -591,12 +586,10 @@ def conv_wgrad(dy, x, k, s, p, out=None, ring=0, batch=None, tile=None, slots=0,
 # ----------------------------------------------------------------------------
 # batch norm
 # ----------------------------------------------------------------------------
-import os as _os
-_WHATIF = int(_os.environ.get("VS_WHATIF", "0"))  # tools only: skip launches to measure what they cost on the step
-_BN_TWO_LEVEL = int(_os.environ.get("VS_BN_TWO_LEVEL", "512"))  # partial rows above which a level-1 reduce runs first
+_BN_TWO_LEVEL = switches.read("VS_BN_TWO_LEVEL")  # partial rows above which a level-1 reduce runs first
 # the BN finalizes (forward and backward) as ONE launch each whatever the number of partial rows (vs_bn_finalize_ws /
 # vs_bn_bwd_finalize_ws); VS_BN_FIN2=0: the round-4 launches (A/B)
-BN_FIN2 = _os.environ.get("VS_BN_FIN2", "1") != "0"
+BN_FIN2 = switches.read("VS_BN_FIN2")
 _fin_ws = [0]
 _whatif_const = {}
 
@@ -894,7 +887,7 @@ def linear_fwd(x, w, b=None, relu=False):
     return y
 
 
-_LINEAR_BWD_FUSED = _os.environ.get("VS_LINEAR_BWD_FUSED", "1") != "0"  # A/B: 0 = relu_bwd + bwd_data + bwd_weight launches
+_LINEAR_BWD_FUSED = switches.read("VS_LINEAR_BWD_FUSED")  # A/B: 0 = relu_bwd + bwd_data + bwd_weight launches
 
 
 def linear_bwd(dy, x, w, need_dx=True, has_bias=True, dw_out=None, db_out=None, wt=None, relu_y=None, dx_res=None):

@@ -21,12 +21,11 @@ best first).  Differences, all deliberate:
   lm_model (unused by the reference's configs: they raise).
 """
 import math
-import os
 
 import torch
 from torch import nn
 
-from . import ops
+from . import ops, switches
 from .hf_gpt2_fseq import KVCacheState
 
 
@@ -108,7 +107,7 @@ class _DeviceSearchSession:
         self.pool = None
         self.epoch = None
         self.enc = None
-        self.use_graphs = self.kv and os.environ.get("VS_GEN_GRAPHS", "1") != "0"
+        self.use_graphs = self.kv and switches.read("VS_GEN_GRAPHS")
 
     def _reset(self, prefix_tokens, bos_token):
         self.tok[0].fill_(self.pad)

@@ -24,10 +24,11 @@ one process per MI355X over RCCL:
 A failed hipGraph capture RAISES (bench.py then exits non-zero): a silently eager multi-GPU line
 would be a different measurement under the same name.
 """
-import os
 
 import torch
 import torch.distributed as dist
+
+from . import switches
 
 
 class TrainStep:
@@ -42,7 +43,7 @@ class TrainStep:
         can_overlap = self.trunk is not None and hasattr(self.trunk, "BWD_SEGMENTS")
         self.overlap = (self.use_dist and world > 1 if overlap is None else bool(overlap)) and can_overlap
         # single process: ranged Adam beside the backward pass (needs the segmented backward and the arena on a GPU)
-        want = os.environ.get("VS_ADAM_OVERLAP", "0") not in ("0", "") if adam_overlap is None else bool(adam_overlap)
+        want = switches.read("VS_ADAM_OVERLAP") != 0 if adam_overlap is None else bool(adam_overlap)
         if adam_overlap and getattr(opt, "max_grad_norm", None) is not None:
             # the early ranges would be updated before the last segment's gradients -- part of the norm -- exist
             raise ValueError("TrainStep: adam_overlap=True cannot be combined with the optimizer's max_grad_norm "
@@ -66,9 +67,9 @@ class TrainStep:
         #       so a clean capture covers every replay).
         #   False: never.
         # VS_GRAD_FILL=0 / 1 / learn overrides (A/B runs).
-        env = os.environ.get("VS_GRAD_FILL", "")
-        if env in ("0", "1", "learn"):
-            grad_fill = {"0": False, "1": True, "learn": "learn"}[env]
+        env = switches.read("VS_GRAD_FILL")
+        if env is not None:
+            grad_fill = env
         if grad_fill is None:  # round-2 spelling of "learn"
             grad_fill = "learn"
         self.grad_fill = grad_fill
@@ -146,7 +147,7 @@ class TrainStep:
     # section between the trunk's forward and backward leaves the chip idle -- so, when the model has a
     # `vid_feat_encoder` (the first module behind the trunk), the refresh is launched from a forward pre-hook on it
     # (and right after the forward pass if that module never ran).  VS_TRANSPOSE_LATE=0: at the start of the step.
-    late_transposes = os.environ.get("VS_TRANSPOSE_LATE", "1") != "0"
+    late_transposes = switches.read("VS_TRANSPOSE_LATE")
 
     def _adam(self):
         self.opt.step(world=self.world, defer_transposes=True, grad_bf16=self.grad_bf16)
@@ -183,7 +184,7 @@ class TrainStep:
             self._adam_stream = torch.cuda.Stream(device=self.arena.data.device)
         side = self._adam_stream
         self.opt.tick()
-        late = os.environ.get("VS_ADAM_OVERLAP") == "2"  # A/B: the segmented backward, every range updated at the end
+        late = switches.read("VS_ADAM_OVERLAP") == 2  # A/B: the segmented backward, every range updated at the end
         for fn, (lo, hi) in self.segments:
             fn()
             if late:

@@ -9,12 +9,11 @@ reductions).  Parity trap kept: the softmax scale is sqrt(d_model), not
 sqrt(head_dim) (`utils/transformer_code.py:36,54`).
 """
 import math
-import os
 
 import torch
 from torch import nn
 
-from . import ops
+from . import ops, switches
 
 
 class LinearFn(torch.autograd.Function):
@@ -224,7 +223,7 @@ class ResidualBlock(nn.Module):
     # launch (12 per step on the critical path of the 8-token section).  Instead the LayerNorm's backward hands its
     # dx to the layer's first op (a dict both hold), whose data-gradient kernel adds it in its epilogue
     # (`vs_linear_bwd_fused_res`): the same sum, rounded once.  VS_RESIDUAL_ROUTE=0 = autograd's add.
-    route_grads = os.environ.get("VS_RESIDUAL_ROUTE", "1") != "0"
+    route_grads = switches.read("VS_RESIDUAL_ROUTE")
 
     def forward(self, *x):
         route = None

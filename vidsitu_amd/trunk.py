@@ -17,12 +17,11 @@ tensors handed back keep the reference's logical NCDHW shape.
          `param.grad` (one fp32 arena), so DDP-style averaging is one all-reduce.
 """
 import contextlib
-import os
 
 import torch
 from torch import nn
 
-from . import ops
+from . import ops, switches
 
 STAGE_DEPTH = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), "tiny": (1, 0, 0, 1), "mini": (1, 1, 1, 1)}
 TEMPORAL_KERNEL_BASIS = {
@@ -156,7 +155,7 @@ class _WgradLanes:
     the issuing stream starts the next unit's BN kernels costs ~25 us per unit under replay (16.1-16.3 ms vs 13.4-13.5).
     VS_WGRAD_LANES=0: off."""
 
-    enabled = os.environ.get("VS_WGRAD_LANES", "1") != "0"
+    enabled = switches.read("VS_WGRAD_LANES")
     # device index -> [issuing stream, lane stream, queue of (event, keepalive) per launched unit].  Lane streams
     # are created once (never inside a hipGraph capture, where creating a stream is an unsafe call).
     lanes = {}
@@ -212,14 +211,14 @@ class _Unit:
     trace = None  # debugging: set to a list to record (conv, y, z, mean, invstd) per unit
     # BN-backward sums of the a / b units of a bottleneck emitted by the consuming convolution's dgrad
     # epilogue (vs_conv_dgrad_bnstats) instead of a reduce pass of their own; VS_FUSE_BN_SUMS=0 = A/B switch
-    fuse_bn_sums = os.environ.get("VS_FUSE_BN_SUMS", "1") != "0"
-    fuse_sc_sums = os.environ.get("VS_FUSE_SC_SUMS", "1") != "0"  # the shortcut unit's sums from the same epilogue
+    fuse_bn_sums = switches.read("VS_FUSE_BN_SUMS")
+    fuse_sc_sums = switches.read("VS_FUSE_SC_SUMS")  # the shortcut unit's sums from the same epilogue
     # data gradient + weight gradient of a unit as ONE launch where both run on the 128 x 128 ring kernels
     # (ops.conv_pair): no side lane, hence no fork / join edge pair (~17 us in a replayed graph).  VS_CONV_PAIR=0: lanes.
-    pair_launch = os.environ.get("VS_CONV_PAIR", "1") != "0"
+    pair_launch = switches.read("VS_CONV_PAIR")
     # Eval only: split bf16 weights W = W_hi + W_lo, two launches per convolution (north_star's "logits within 1e-3 of
     # the reference": met in this mode, at about half the clips/s).  VS_EVAL_SPLIT_WEIGHTS=1.
-    split_weights = os.environ.get("VS_EVAL_SPLIT_WEIGHTS", "0") == "1"
+    split_weights = switches.read("VS_EVAL_SPLIT_WEIGHTS")
     _zeros = {}
 
     # VideoTrunk.calibrate_weight_rounding: a dict while the calibration pass runs (conv -> measured input means)
@@ -445,11 +444,11 @@ class ResNetBasicStem(nn.Module):
     # train mode: BN + ReLU + pool in one pass (ops.bn_apply_maxpool): the full-resolution normalised tensor -- 154 MB for
     # the two stems of SlowFast-R50 at 8 clips -- is neither written nor re-read.  VS_STEM_POOL_FUSE=0: separate launches.
     # (The pool's backward inside the BN-backward passes, ops.bn_bwd(pool_src=...), exists as well.)
-    fuse_pool = os.environ.get("VS_STEM_POOL_FUSE", "1") != "0"
+    fuse_pool = switches.read("VS_STEM_POOL_FUSE")
     # the backward half is off by default: measured alone (tools/stem_pool_time.py) the forward pass is 62 vs 80 us
     # (slow stem) and 26 vs 42 us (fast stem), but gathering the pool's gradient inside BOTH backward passes costs
     # more instructions than the dense tensor costs bytes: 202 vs 149 us and 126 vs 83 us.  VS_STEM_POOL_FUSE_BWD=1.
-    fuse_pool_bwd = os.environ.get("VS_STEM_POOL_FUSE_BWD", "0") == "1"
+    fuse_pool_bwd = switches.read("VS_STEM_POOL_FUSE_BWD")
 
     def fwd(self, x, out, train, saved):
         if train and ResNetBasicStem.fuse_pool and _Unit.trace is None:
@@ -514,10 +513,10 @@ class ResBlock(nn.Module):
     # Eval only: the identity chain of a stage kept in fp32 (ops.residual_add_f32; north_star's "logits within 1e-3").
     # The block's bf16 output carries the fp32 stream as the attribute `_vs_f32` for the next block of the stage.
     # Costs one element-wise pass per block (the c unit's residual + ReLU epilogue becomes that pass).  VS_RESIDUAL_FP32=1.
-    residual_fp32 = os.environ.get("VS_RESIDUAL_FP32", "0") == "1"
+    residual_fp32 = switches.read("VS_RESIDUAL_FP32")
     # Eval only: conv b and conv c of the fast pathway's 8 / 16 / 32-channel bottlenecks (res2 - res4) as one launch
     # (ops.conv_fwd_bc: the inner tensor stays in LDS).  VS_EVAL_FUSE_BC=0: two launches (A/B switch).
-    fuse_bc = os.environ.get("VS_EVAL_FUSE_BC", "1") != "0"
+    fuse_bc = switches.read("VS_EVAL_FUSE_BC")
 
     def _bc_fusable(self, a):
         b2 = self.branch2
@@ -603,13 +602,11 @@ class ResBlock(nn.Module):
 
 
     # blocks whose weight gradients share one grouped launch (VS_WGRAD_GROUP_SPAN)
-    group_span = int(os.environ.get("VS_WGRAD_GROUP_SPAN", "3"))  # A/B in the step: 1 -> 2 -> 3 blocks +0.2 % each, 4 the same, 6 -0.3 %
+    group_span = switches.read("VS_WGRAD_GROUP_SPAN")  # A/B in the step: 1 -> 2 -> 3 blocks +0.2 % each, 4 the same, 6 -0.3 %
 
-    # Train: a block's weight gradients as one launch.  VS_WGRAD_GROUP=0: per-unit launches; VS_WGRAD_GROUP_MAXP: the
-    # position count up to which a block is grouped (at 32 clips per GPU the separate launches fill the chip themselves).
-    group_wgrads = os.environ.get("VS_WGRAD_GROUP", "1") != "0"
-    group_max_positions = int(os.environ.get("VS_WGRAD_GROUP_MAXP", "1000000000"))
-    group_min_channels = int(os.environ.get("VS_WGRAD_GROUP_MINC", "128"))  # narrower blocks: neutral (64, 32) or slower (16, 8) in the step
+    # Train: a block's weight gradients as one launch.  VS_WGRAD_GROUP=0: per-unit launches.
+    group_wgrads = switches.read("VS_WGRAD_GROUP")
+    group_min_channels = switches.read("VS_WGRAD_GROUP_MINC")  # narrower blocks: neutral (64, 32) or slower (16, 8) in the step
 
     def _wgrad_grouped(self, rc, rb, ra, rsc, dout):
         if not ResBlock.group_wgrads or not dout.is_cuda:
@@ -628,8 +625,6 @@ class ResBlock(nn.Module):
                     hit = False
                     break
                 items.append((y, x, c.k, c.s, c.p, torch.empty(0)))
-            if hit:
-                hit = min(ops.act_rows(r["y"]) for r in recs) <= ResBlock.group_max_positions
             if hit:
                 # (the plan query needs descriptors only: the raw conv output stands in for its gradient, same shape / pitch)
                 probe = [(y, x, k, s_, p, torch.empty((y.shape[1], *k, x.shape[1]), dtype=torch.float32,
@@ -683,9 +678,9 @@ class ResBlock(nn.Module):
 
     # Train, backward: the c unit's and the shortcut unit's BN-backward apply as one pass (ops.bn_bwd_apply2): the block's
     # output gradient and its ReLU bits are read once.  VS_FUSE_SC_BWD=0: two passes.
-    fuse_sc_bwd = os.environ.get("VS_FUSE_SC_BWD", "1") != "0"
+    fuse_sc_bwd = switches.read("VS_FUSE_SC_BWD")
     # Train: the shortcut unit's BN apply inside the c unit's apply pass (ops.bn_apply2).  VS_FUSE_SC_APPLY=0: two passes.
-    fuse_sc_apply = os.environ.get("VS_FUSE_SC_APPLY", "1") != "0"
+    fuse_sc_apply = switches.read("VS_FUSE_SC_APPLY")
 
 
 class Nonlocal(nn.Module):
@@ -982,7 +977,7 @@ class VideoTrunk(nn.Module):
     """`SlowFast_FeatModel` / `ResNet_FeatModel` (mdl_sf_base.py:20-62)."""
 
     # run the two pathways of a multi-pathway trunk on two streams (VS_DUAL_STREAM=0: one stream)
-    dual_stream = os.environ.get("VS_DUAL_STREAM", "1") != "0"
+    dual_stream = switches.read("VS_DUAL_STREAM")
     # Fork + full join around every stage.  A one-directional variant (fork once per pass, the slow
     # pathway waits for the fast one only at the lateral connections, so the fast pathway may run
     # ahead) was measured SLOWER: train 16.85 vs 16.47 ms, forward 3.17 vs 2.96 ms at batch 8.
@@ -1437,7 +1432,7 @@ class VideoTrunk(nn.Module):
     # next fork -- instead of on the caller's stream between two stages: nothing of the slow pathway's chain waits for
     # them but the join it waits at anyway, and their strided data gradients (55 / 31 / 20 / 20 us) leave the chain.
     # Same launches, same bits.  VS_FUSE_ON_FAST=0: on the caller's stream.
-    fuse_on_fast = os.environ.get("VS_FUSE_ON_FAST", "1") != "0"
+    fuse_on_fast = switches.read("VS_FUSE_ON_FAST")
 
     def _fuse_bwd(self, saved, d, defer=False):
         """-> ([slow gradient, fast gradient], None), or with `defer` ([slow gradient, None], thunk): the thunk runs the

@@ -779,6 +779,26 @@ int vs_gelu_erf_bwd(const float* dy, const float* x_pre, float* dx, int64_t n, v
 int vs_tanh_fwd(const float* x, float* y, int64_t n, void* stream);
 int vs_tanh_bwd(const float* dy, const float* y, float* dx, int64_t n, void* stream);
 
+/* ---- Key-tiled self-attention, csrc/attn_tiled.hip, fp32 on v_mfma_f32_16x16x4_f32: the family for the sequences the
+ * LDS-resident kernels (vs_attn_pad_*, vs_attn_causal_*) refuse.  K and V pass through LDS in tiles of 64 keys under an
+ * online softmax, so LDS does not depend on L; every L >= 1 is accepted (up to 65535 * 64), dh is 16, 32, 64 or 128.
+ * causal = 0: vs_attn_pad_fwd's masking rule; causal != 0: vs_attn_causal_fwd's (-1e4 arithmetic, literally).
+ * snap == NULL: no dropout (thr must then be 0); otherwise dropout on the probabilities with the element index of the
+ * resident kernels, ((r*H + h)*L + i)*Lp4 + j with Lp4 = (L + 3) & ~3 -- the mask depends on the element alone, so the
+ * forward and backward of a step may come from different families.
+ * The backward re-derives p (the forward stores nothing): launch A writes each query's row statistics and
+ * D_i = sum_j p_ij dP_ij to the scratch ([R*H][3][L] floats, vs_attn_tiled_bwd_scratch_bytes) and dQ, launch B reads
+ * them for dK and dV.  No atomics, fixed summation order.  Bad arguments or a short scratch: an error, nothing written. */
+int vs_attn_tiled_fwd(const float* qkv, const uint8_t* key_mask, float* out, int R, int L, int H, int dh, int causal,
+                      const int64_t* snap, uint32_t site, uint32_t thr, float scale, void* stream);
+size_t vs_attn_tiled_bwd_scratch_bytes(int R, int L, int H);
+int vs_attn_tiled_bwd(const float* qkv, const uint8_t* key_mask, const float* dout, float* dqkv, void* scratch,
+                      size_t scratch_bytes, int R, int L, int H, int dh, int causal, const int64_t* snap,
+                      uint32_t site, uint32_t thr, float scale, void* stream);
+/* 1 where the LDS-resident attention of this rule (causal != 0: vs_attn_causal_*, else vs_attn_pad_*) and direction
+ * (backward != 0) holds sequences of L positions at head width dh, by the launchers' own formulas; else 0. */
+int vs_attn_resident_fits(int causal, int L, int dh, int backward);
+
 #ifdef __cplusplus
 }
 #endif

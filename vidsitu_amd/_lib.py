@@ -218,7 +218,11 @@ SIGNATURES = {
     "vs_attn_pad_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "vs_attn_pad_bwd_scratch_bytes": (_sz, [_i, _i, _i]),
     "vs_attn_pad_bwd": (_i, [_p, _p, _p, _p, _p, _sz, _i, _i, _i, _i, _p]),
-    "vs_roberta_embed": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "vs_attn_tiled_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _u32, _u32, _f, _p]),
+    "vs_attn_tiled_bwd_scratch_bytes": (_sz, [_i, _i, _i]),
+    "vs_attn_tiled_bwd": (_i, [_p, _p, _p, _p, _p, _sz, _i, _i, _i, _i, _i, _p, _u32, _u32, _f, _p]),
+    "vs_attn_resident_fits": (_i, [_i, _i, _i, _i]),
+    "vs_roberta_embed": (_i,[_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "vs_gelu_erf_fwd": (_i, [_p, _p, _i64, _p]),
     "vs_gelu_erf_bwd": (_i, [_p, _p, _p, _i64, _p]),
     "vs_tanh_fwd": (_i, [_p, _p, _i64, _p]),

@@ -6,6 +6,7 @@
 // are gemm_nt.hip's.
 #include <math.h>
 
+#include "attn_shared.h"
 #include "common.h"
 #include "dropout_rng.h"
 
@@ -67,7 +68,7 @@ extern "C" int vs_gpt2_embed_drop(const int64_t* tokens, const float* wte, const
 // ----------------------------------------------------------------------------
 // Grid = (r, head) x chunks of AC_QC queries: 160 blocks of 60 queries each were a latency-bound launch
 // (91 us per layer); a chunk's block loads the K rows up to its last query and all V rows.
-#define AC_QC 16
+// (AC_QC = 16 queries per block and the LDS formulas: attn_shared.h)
 
 // Dropout on one query's row of attention probabilities, in LDS, by the wave that owns the row: row[j] becomes
 // MUL ? row[j] * m_j : m_j with m_j = scale or 0.  Element index = rowblk * 4 + j where rowblk * 4 =
@@ -152,12 +153,12 @@ template <bool DROP>
 static int attn_causal_fwd_launch(const float* qkv, const uint8_t* key_mask, float* out, int R, int L, int H,
                                   int dh, DropArgs dr, void* stream) {
   VS_CHECK_ARG(qkv && out && R > 0 && L > 0 && H > 0 && dh > 0, "bad args");
-  const size_t smem = ((size_t)2 * L * (dh + 1) + 4 * L + 4 * dh) * sizeof(float);
-  VS_CHECK_ARG(smem <= 160 * 1024, "sequence too long for the LDS-resident attention (L*dh)");
+  const size_t smem = ac_fwd_smem(L, dh);
+  VS_CHECK_ARG(smem <= AC_LDS_MAX, "sequence too long for the LDS-resident attention (L*dh)");
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)attn_causal_kernel<DROP>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                              hipFuncAttributeMaxDynamicSharedMemorySize, AC_LDS_MAX);
     attr = true;
   }
   hipLaunchKernelGGL(attn_causal_kernel<DROP>, dim3(R * H, (L + AC_QC - 1) / AC_QC), dim3(256), smem,
@@ -1064,16 +1065,15 @@ static int attn_causal_bwd_launch(const float* qkv, const uint8_t* key_mask, con
                                   void* stream) {
   VS_CHECK_ARG(qkv && dout && dqkv && scratch && R > 0 && L > 0 && H > 0 && dh > 0, "bad args");
   VS_CHECK_ARG(scratch_bytes >= vs_attn_causal_bwd_scratch_bytes(R, L, H), "scratch too small");
-  const size_t smem_q = ((size_t)(2 * L + 2 * AC_QC) * (dh + 1) + 8 * L) * sizeof(float);
-  const size_t smem_kv = ((size_t)2 * L * (dh + 1) + 2 * L * AC_QC) * sizeof(float);
-  VS_CHECK_ARG(smem_q <= 160 * 1024 && smem_kv <= 160 * 1024,
+  const size_t smem_q = ac_bwd_q_smem(L, dh), smem_kv = ac_bwd_kv_smem(L, dh);
+  VS_CHECK_ARG(smem_q <= AC_LDS_MAX && smem_kv <= AC_LDS_MAX,
                "sequence too long for the LDS-resident attention backward");
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)attn_causal_bwd_q_kernel<DROP>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                              hipFuncAttributeMaxDynamicSharedMemorySize, AC_LDS_MAX);
     (void)hipFuncSetAttribute((const void*)attn_causal_bwd_kv_kernel,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                              hipFuncAttributeMaxDynamicSharedMemorySize, AC_LDS_MAX);
     attr = true;
   }
   const dim3 grid(R * H, (L + AC_QC - 1) / AC_QC);

@@ -4,8 +4,8 @@
 // the reference pins.
 #include <math.h>
 
+#include "attn_shared.h"
 #include "common.h"
-#include "dropout_rng.h"
 
 // ----------------------------------------------------------------------------
 // Self-attention over a fused qkv buffer [R, L, 3D]:
@@ -18,50 +18,8 @@
 // its Q fragments live in registers, its score tile [16][Lp] in a private LDS strip, never in memory.
 // Operand maps of the instruction: A[lane & 15][lane >> 4], B[lane >> 4][lane & 15], D[(lane >> 4) * 4 + reg][lane & 15].
 // ----------------------------------------------------------------------------
-#define AP_QT 64
-// dynamic LDS a block may ask for: the 160 KiB of a CU less 1 KiB for the compiler's own static LDS (the block-wide
-// "or" below keeps its flag there; with the full 160 KiB hipFuncSetAttribute refuses the kernel)
-#define AP_LDS_MAX (159 * 1024)
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// rows 0 .. L-1 of a [L][DH] slice (row pitch `stride` floats) into LDS [Lp][DH + 4]; rows L .. Lp-1 are zero
-template <int DH>
-__device__ __forceinline__ void ap_stage(float* dst, const float* src, long long stride, int L, int Lp) {
-  constexpr int LD = DH + 4, V4 = DH / 4;
-  for (int i = threadIdx.x; i < Lp * V4; i += 256) {
-    const int j = i / V4, c = i - j * V4;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (j < L) v = *(const float4*)(src + (long long)j * stride + c * 4);
-    *(float4*)(dst + j * LD + c * 4) = v;
-  }
-}
-
-// The additive mask without its rounding: -1e4 on a score leaves the sum with an ulp of 2^-10, and exp(s - 1e4 - max)
-// is exactly zero (in fp64 too) beside any key that is not masked.  So: a sequence with at least one valid key gives
-// its masked keys the score -inf (weight exactly 0); a sequence whose mask is all zero has the same -1e4 on every
-// key, which the softmax does not see -- it runs unmasked.  Both equal the stated formula for |s| < 9e3.
-// -> true when masked keys are to be dropped; every thread of the block must call it.
-__device__ __forceinline__ bool ap_any_key_valid(const uint8_t* kmask, int r, int L) {
-  int any = 0;
-  if (kmask)
-    for (int j = threadIdx.x; j < L; j += 256) any |= kmask[(long long)r * L + j];
-  return __syncthreads_or(any) != 0;
-}
-
-// DROP (train-mode dropout on the probabilities, out_i = sum_j p_ij m_ij v_j with the row sum taken before the mask):
-// element index of (r, h, i, j) = ((r * H + h) * L + i) * Lp4 + j with Lp4 = (L + 3) & ~3 -- the causal kernel's
-// convention, not this kernel's 16-wide Lp -- so four consecutive keys of a query are one Philox block.  The softmax
-// passes give a row's four lanes the columns c0, c0 + 4, ...; the mask passes give them whole blocks (columns 4b ..
-// 4b + 3 for b = c0, c0 + 4, ...): one draw per four keys, and the plain kernel's summation order stays as it is.
-// -> the four multipliers (0 or scale) of block b of the row whose first block is rowblk
-__device__ __forceinline__ float4 ap_mask4(const DropArgs& dr, uint64_t seed, uint64_t step, uint64_t rowblk, int b) {
-  const vs_philox_out w = vs_dropout_block(seed, step, dr.site, rowblk + (uint64_t)b);
-  return make_float4(w.w[0] >= dr.thr ? dr.scale : 0.f, w.w[1] >= dr.thr ? dr.scale : 0.f,
-                     w.w[2] >= dr.thr ? dr.scale : 0.f, w.w[3] >= dr.thr ? dr.scale : 0.f);
-}
+// (attn_shared.h: AP_QT, AP_LDS_MAX, mfma4, ap_stage, ap_any_key_valid -- the masking rule --, ap_mask4 -- the dropout
+// draw --, and the LDS formulas ap_fwd_smem / ap_bwd_smem)
 
 template <int DH, bool DROP>
 __global__ __launch_bounds__(256) void attn_pad_fwd_kernel(const float* __restrict__ qkv,
@@ -162,17 +120,6 @@ __global__ __launch_bounds__(256) void attn_pad_fwd_kernel(const float* __restri
     }
   }
 }
-
-static inline int ap_lp(int L) { return (L + 15) / 16 * 16; }
-static inline size_t ap_fwd_smem(int L, int dh) {
-  const int Lp = ap_lp(L);
-  return ((size_t)2 * Lp * (dh + 4) + 4 * 16 * (Lp + 4)) * sizeof(float);
-}
-static inline size_t ap_bwd_smem(int L, int dh) {
-  const int Lp = ap_lp(L);
-  return ((size_t)2 * Lp * (dh + 4) + 8 * 16 * (Lp + 4)) * sizeof(float);
-}
-static inline bool ap_dh_ok(int dh) { return dh == 16 || dh == 32 || dh == 64 || dh == 128; }
 
 static bool ap_lds_attr(const void* kernel) {
   const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, AP_LDS_MAX);

@@ -1369,10 +1369,36 @@ def gpt2_embed(tokens, wte, wpe, pos0=0, drop=None):
     return out
 
 
+# ---- whole-sequence attention: the LDS-resident kernels where they hold the sequence, the key-tiled family past them
+def _attn_resident_fits(causal, l, dh, backward):
+    """vs_attn_resident_fits: does the resident kernel of this masking rule and direction hold (L, dh)?  Asked per
+    direction -- the backward's limit is the lower one, and the dropout mask is a function of the element alone, so a
+    resident forward may meet a tiled backward."""
+    return bool(_lib.load().vs_attn_resident_fits(int(causal), int(l), int(dh), int(backward)))
+
+
+def _attn_tiled(qkv, key_mask, out, r, l, n_head, dh, causal, drop):
+    snap, site, thr, scale = (None, 0, 0, 1.0) if drop is None else drop
+    _lib.call("vs_attn_tiled_fwd", _ptr(qkv), _ptr(key_mask), _ptr(out), r, l, n_head, dh, int(causal), _ptr(snap),
+              int(site), int(thr), float(scale), _stream())
+    return out
+
+
+def _attn_tiled_bwd(qkv, key_mask, dout, dqkv, r, l, n_head, dh, causal, drop):
+    ws = _workspace(_lib.load().vs_attn_tiled_bwd_scratch_bytes(r, l, n_head), qkv.device)
+    snap, site, thr, scale = (None, 0, 0, 1.0) if drop is None else drop
+    _lib.call("vs_attn_tiled_bwd", _ptr(qkv), _ptr(key_mask), _ptr(dout), _ptr(dqkv), _ptr(ws),
+              C.c_size_t(ws.numel()), r, l, n_head, dh, int(causal), _ptr(snap), int(site), int(thr), float(scale),
+              _stream())
+    return dqkv
+
+
 def attn_causal(qkv, key_mask, r, l, n_head, drop=None):
     """qkv f32 [R*L, 3D]; key_mask uint8 [R, L] or None -> f32 [R*L, D]."""
     d = qkv.shape[1] // 3
     out = torch.empty((r * l, d), dtype=torch.float32, device=qkv.device)
+    if not _attn_resident_fits(True, l, d // n_head, False):
+        return _attn_tiled(qkv, key_mask, out, r, l, n_head, d // n_head, True, drop)
     if drop is not None:
         snap, site, thr, scale = drop
         _lib.call("vs_attn_causal_drop_fwd", _ptr(qkv), _ptr(key_mask), _ptr(out), r, l, n_head, d // n_head,
@@ -1488,6 +1514,8 @@ def colsum_f32(x, out=None):
 def attn_causal_bwd(qkv, key_mask, dout, r, l, n_head, drop=None):
     d = qkv.shape[1] // 3
     dqkv = torch.empty_like(qkv)
+    if not _attn_resident_fits(True, l, d // n_head, True):
+        return _attn_tiled_bwd(qkv, key_mask, _f32c(dout), dqkv, r, l, n_head, d // n_head, True, drop)
     need = _lib.load().vs_attn_causal_bwd_scratch_bytes(r, l, n_head)
     ws = _workspace(need, qkv.device)
     if drop is not None:
@@ -1618,6 +1646,8 @@ def attn_pad(qkv, key_mask, r, l, n_head, drop=None):
     if qkv.shape[0] != r * l or qkv.shape[1] != 3 * d or d % n_head:
         raise _lib.VsError(f"attn_pad: qkv {tuple(qkv.shape)} is not [{r}*{l}, 3*D] with D % {n_head} == 0")
     out = torch.empty((r * l, d), dtype=torch.float32, device=qkv.device)
+    if not _attn_resident_fits(False, l, d // n_head, False):
+        return _attn_tiled(qkv, _key_mask_u8(key_mask, r, l), out, r, l, n_head, d // n_head, False, drop)
     if drop is not None:
         snap, site, thr, scale = drop
         _lib.call("vs_attn_pad_drop_fwd", _ptr(qkv), _ptr(_key_mask_u8(key_mask, r, l)), _ptr(out), r, l, n_head,
@@ -1634,6 +1664,9 @@ def attn_pad_bwd(qkv, key_mask, dout, r, l, n_head, drop=None):
     if qkv.shape[0] != r * l or dout.numel() != r * l * d or d % n_head:
         raise _lib.VsError("attn_pad_bwd: shapes of qkv / dout do not match R, L")
     dqkv = torch.empty_like(qkv)
+    if not _attn_resident_fits(False, l, d // n_head, True):
+        return _attn_tiled_bwd(qkv, _key_mask_u8(key_mask, r, l), _f32c(dout), dqkv, r, l, n_head, d // n_head, False,
+                               drop)
     need = _lib.load().vs_attn_pad_bwd_scratch_bytes(r, l, n_head)
     ws = _workspace(need, qkv.device)
     if drop is not None:

@@ -583,6 +583,24 @@ size_t vs_gemm_nt_bf16_workspace_bytes(int M, int N, int K);
 int vs_gemm_nt_bf16_ws(const float* x, const float* w, const float* b, const float* res, float* y, int M,
                        int N, int K, int act, void* workspace, size_t ws_bytes, void* stream);
 
+/* vs_gemm_nt_bf16_ws whose operands may each be "K-strided": stored [K][rows] (rows contiguous, K the slow axis)
+ * instead of [rows][K].  y[M,N] = act(sum_k bf16(A[m,k]) * bf16(B[n,k]) + bias) + res with a = A as [M][K]
+ * (a_kstrided 0) or [K][M] (1), b = B as [N][K] (b_kstrided 0) or [K][N] (1).  The loader transposes on its way into
+ * LDS and leaves the tile the other form leaves for the transposed copy, so the result equals vs_gemm_nt_bf16_ws on
+ * transposed copies bit for bit.  The two products of a dense layer's backward without a copy: dx = dy . W (b = W
+ * [out][in], b_kstrided) and dW = dy^T . x (a = dy [T][out], b = x [T][in], both strided, K = T).  Workspace:
+ * vs_gemm_nt_bf16_workspace_bytes(M, N, K), same split; unlike vs_gemm_nt_bf16_ws a missing or short one is an error.
+ * With both flags 0 it is that entry.  Every argument is checked before any launch.
+ * vs_gemm_bf16_ld_ws: a K-strided operand may be a row range of a larger array -- element (row, k) at a[k * lda + row]
+ * with a pointing at the first row of the range, lda >= M (ldb >= N) -- so the three weight gradients of a fused
+ * q|k|v projection read their rows of dqkv [T][3D] in place.  A leading dimension of a K-contiguous operand is
+ * ignored; vs_gemm_bf16_ws is lda = M, ldb = N. */
+int vs_gemm_bf16_ws(const float* a, const float* b, const float* bias, const float* res, float* y, int M, int N,
+                    int K, int a_kstrided, int b_kstrided, int act, void* workspace, size_t ws_bytes, void* stream);
+int vs_gemm_bf16_ld_ws(const float* a, const float* b, const float* bias, const float* res, float* y, int M, int N,
+                       int K, int a_kstrided, int b_kstrided, int lda, int ldb, int act, void* workspace,
+                       size_t ws_bytes, void* stream);
+
 /* Decode-step (1..64 rows) GEMM on fragment-major operands.  vs_pack_rows_f32 copies a row-major
  * matrix src[R][K] (K % 16 == 0) into 1-KB blocks of 16 rows x 16 floats in v_mfma_f32_16x16x4_f32
  * operand order (block (r/16, k/16) at index (r/16)*(K/16) + k/16; lane (k%16/4)*16 + r%16 holds floats

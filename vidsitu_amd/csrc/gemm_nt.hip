@@ -12,14 +12,15 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 // An operand policy: LDS element and MFMA fragment type, row pitch LD (elements), k extent KSTEP of one MFMA, LDS
 // alignment, frag_k (k offset of the fragment of lane >> 5), load (one fragment), mfma, and PACKED: store4 converts and
-// stores the four floats of a loader lane (otherwise the kernel stores them as they are).
+// stores the four floats of a loader lane (otherwise the kernel stores them as they are).  A_T / B_T: that operand is
+// stored [K][rows] ("K-strided": rows contiguous, K the slow axis) and takes the strided loader (GemmBf16T only).
 //
 // fp32 operands, the reference's arithmetic (v_mfma_f32_32x32x2_f32, 157 TFLOP/s dense on MI355X).  Odd pitch (33
 // floats): the fragment read of a 32x32x2 MFMA (lane l: row l&31, k = l>>5) is then conflict free.
 struct GemmF32 {
   typedef float elem, frag;
   static constexpr int LD = 33, KSTEP = 2, ALIGN = 4;
-  static constexpr bool PACKED = false;
+  static constexpr bool PACKED = false, A_T = false, B_T = false;
   static __device__ __forceinline__ int frag_k(int fk) { return fk; }
   static __device__ __forceinline__ float load(const float* p) { return *p; }
   static __device__ __forceinline__ f32x16 mfma(float a, float b, const f32x16& c) {
@@ -41,7 +42,7 @@ struct GemmBf16 {
   typedef uint16_t elem;
   typedef bf16x8 frag;
   static constexpr int LD = 40, KSTEP = 16, ALIGN = 16;
-  static constexpr bool PACKED = true;
+  static constexpr bool PACKED = true, A_T = false, B_T = false;
   static __device__ __forceinline__ void store4(uint16_t* dst, const float4& r, bool ok) {
     uint2 v;
     v.x = pack2_bf16(ok ? r.x : 0.f, ok ? r.y : 0.f);
@@ -53,6 +54,24 @@ struct GemmBf16 {
   static __device__ __forceinline__ f32x16 mfma(const bf16x8& a, const bf16x8& b, const f32x16& c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
   }
+};
+
+// The same tiles from K-strided operands: the two products of a dense layer's backward without a transposed copy,
+// dx = dy . W (B = W[out][in] strided) and dW = dy^T . x (A = dy[T][out] and B = x[T][in] both strided, K = T).
+// The strided loader reads along the row axis: a thread owns 4 consecutive rows at the k-pair (2 kp, 2 kp + 1) -- two
+// float4 loads, or 8 scalar ones -- and stores each row's pair as one dword, pack2_bf16(k even, k odd): the rounding
+// of store4.  The tile it leaves is byte for byte the tile the K-contiguous loader leaves for the transposed copy, so
+// everything behind the tile store is shared.  Thread -> (row quad rq of 16, k-pair kp of 16) of a 64-row pass:
+// rq = 8 * (wave & 1) + 4 * (lane >> 5) + (lane & 3), kp = 8 * (wave >> 1) + ((lane >> 2) & 7).  A wave's load is 8
+// segments of 128 contiguous bytes (8 row quads at each of 8 values of k).  ds_write_b32 is served in two groups of
+// 32 lanes on 32 dword banks; row r, pair kp sits at dword 20 r + kp, so the 4 row quads x 8 pairs of a group fall on
+// 16 banks with two addresses each: 2-way, which a ds_write_b32 hides behind its own 4 issue cycles (a store conflict
+// costs time only once the LDS-array cycles exceed them; 16 row quads at 2 pairs, the mapping that loads 256-byte
+// segments, is 8-way).  tools/probes/gemm_bf16_lds_sim.py counts it: 2.00 array cycles per group in every wave.
+// (The compiler pairs the stores of two rows of a quad into one ds_write2_b32: the same two accesses.)
+template <bool AT, bool BT>
+struct GemmBf16T : GemmBf16 {
+  static constexpr bool A_T = AT, B_T = BT;
 };
 
 // Epilogue of one wave's MR x NR block of 32x32 accumulators (the D layout of a 32x32 MFMA does not depend on the
@@ -95,102 +114,25 @@ __device__ __forceinline__ void gemm_tile_epilogue(const f32x16 (&acc)[BM / 64][
 // tile into slab z of `y` (M * N floats each); gemm_splitk_reduce_kernel adds the slabs in slice order and
 // applies the epilogue.  Layers with few output tiles (600 x 1024: 160 tiles of 64 x 64 for 256 CUs) then
 // run 3-4 blocks per CU and overlap each other's memory latency.
-template <class Op, int BM, int BN, bool KVEC>  // 128x128 (2x2 MFMA tiles per wave) or 64x64 (one per wave); K % 4 == 0
+// KVEC: every operand takes 16-byte loads (K-contiguous: K % 4 == 0; K-strided: row count and leading dimension
+// % 4 == 0; bases aligned).
+template <class Op, int BM, int BN, bool KVEC>  // 128x128 (2x2 MFMA tiles per wave) or 64x64 (one per wave)
 __global__ __launch_bounds__(256) void gemm_nt_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                       const float* __restrict__ bias, const float* res, float* y,
                                                       int M, int N, int K, int act, int kts) {
-  typedef typename Op::elem elem;
-  constexpr int LD = Op::LD;
-  constexpr int MR = BM / 64, NR = BN / 64;  // 32x32 accumulators per wave
-  constexpr int PA = BM / 32, PB = BN / 32;  // loader passes (32 rows each)
-  __shared__ __attribute__((aligned(Op::ALIGN))) elem As[2][BM * LD];
-  __shared__ __attribute__((aligned(Op::ALIGN))) elem Bs[2][BN * LD];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-  // loader mapping: 8 float4 per 32-float row, 32 rows per pass
-  const int lc = tid & 7, lr = tid >> 3;
-  constexpr bool kvec = KVEC;  // compile time: a runtime flag put every load behind a branch (and a wait)
-  float4 ra[PA], rb[PB];
+  constexpr int lda = 0, ldb = 0;  // no strided operand
+#include "gemm_tile_body.inc"
+}
 
-  // Loads are branch-free (a load inside `if (ok)` sits in its own basic block behind its own wait: the 8
-  // loads of a k-tile were 8 serialised round trips) and RAW: out-of-range lanes read element 0 and are
-  // zeroed only when the tile is written to LDS, so nothing touches the loaded registers -- and no wait is
-  // placed -- before the MFMAs of the current tile have been issued.
-  unsigned okmask = 0;
-  auto ld4 = [&](const float* base, int row, int rows, int k, int bit) __attribute__((always_inline)) {
-    const bool ok = row < rows && k < K;
-    okmask = ok ? (okmask | (1u << bit)) : (okmask & ~(1u << bit));
-    if constexpr (kvec) return *(const float4*)(base + (ok ? (long long)row * K + k : 0));
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ok) {
-      const float* s = base + (long long)row * K + k;
-      v.x = s[0]; if (k + 1 < K) v.y = s[1]; if (k + 2 < K) v.z = s[2]; if (k + 3 < K) v.w = s[3];
-    }
-    return v;
-  };
-  auto gload = [&](int k0) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < PA; ++i) ra[i] = ld4(x, m0 + lr + 32 * i, M, k0 + lc * 4, i);
-#pragma unroll
-    for (int i = 0; i < PB; ++i) rb[i] = ld4(w, n0 + lr + 32 * i, N, k0 + lc * 4, PA + i);
-  };
-  // The unconverted stores stand here and not behind a function of the policy: routed through one (member, lambda,
-  // by value or by reference), the fp32 128x128 kernel gets another register assignment with the same instructions
-  // and runs 3 % (N = 3072) to 12 % (N = 4096) slower at 3000 x N x 1024 (profiles/gemm_unify.txt).
-  auto sstore = [&](int buf) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < PA; ++i) {
-      elem* a = &As[buf][(lr + 32 * i) * LD + lc * 4];
-      const bool ok = (okmask >> i) & 1;
-      if constexpr (Op::PACKED) Op::store4(a, ra[i], ok);
-      else {
-        a[0] = ok ? ra[i].x : 0.f; a[1] = ok ? ra[i].y : 0.f; a[2] = ok ? ra[i].z : 0.f; a[3] = ok ? ra[i].w : 0.f;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < PB; ++i) {
-      elem* b = &Bs[buf][(lr + 32 * i) * LD + lc * 4];
-      const bool ok = (okmask >> (PA + i)) & 1;
-      if constexpr (Op::PACKED) Op::store4(b, rb[i], ok);
-      else {
-        b[0] = ok ? rb[i].x : 0.f; b[1] = ok ? rb[i].y : 0.f; b[2] = ok ? rb[i].z : 0.f; b[3] = ok ? rb[i].w : 0.f;
-      }
-    }
-  };
-
-  f32x16 acc[MR][NR] = {};
-
-  const int fr = lane & 31, fk = lane >> 5;
-  const int nk_all = (K + GM_BK - 1) / GM_BK;
-  const bool split = gridDim.z > 1;
-  const int kt0 = split ? blockIdx.z * kts : 0;
-  const int nk = split ? min(nk_all, kt0 + kts) : nk_all;
-  if (split) y += (long long)blockIdx.z * M * N;
-  gload(kt0 * GM_BK);
-  sstore(kt0 & 1);
-  __syncthreads();
-  for (int kt = kt0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) gload((kt + 1) * GM_BK);
-    const elem* A = &As[cur][(wm * (BM / 2) + fr) * LD + Op::frag_k(fk)];
-    const elem* B = &Bs[cur][(wn * (BN / 2) + fr) * LD + Op::frag_k(fk)];
-#pragma unroll
-    for (int ks = 0; ks < GM_BK; ks += Op::KSTEP) {
-      typename Op::frag av[MR], bv[NR];
-#pragma unroll
-      for (int a = 0; a < MR; ++a) av[a] = Op::load(A + a * 32 * LD + ks);
-#pragma unroll
-      for (int b = 0; b < NR; ++b) bv[b] = Op::load(B + b * 32 * LD + ks);
-#pragma unroll
-      for (int a = 0; a < MR; ++a)
-#pragma unroll
-        for (int b = 0; b < NR; ++b) acc[a][b] = Op::mfma(av[a], bv[b], acc[a][b]);
-    }
-    if (kt + 1 < nk) sstore(cur ^ 1);
-    __syncthreads();
-  }
-  gemm_tile_epilogue<BM, BN>(acc, bias, res, y, M, N, m0 + wm * (BM / 2), n0 + wn * (BN / 2), lane, act, split);
+// The strided forms carry the leading dimension of each strided operand: the row count of the array it is a row range
+// of (dqkv[T][3D] feeds three weight gradients of D rows each).  The kernel text is the one above, and is included
+// rather than called: behind a function the fp32 kernels get another register assignment (profiles/gemm_unify.txt),
+// and two more kernel arguments would move the ones the runtime appends.
+template <class Op, int BM, int BN, bool KVEC>
+__global__ __launch_bounds__(256) void gemm_ld_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                      const float* __restrict__ bias, const float* res, float* y,
+                                                      int M, int N, int K, int act, int kts, int lda, int ldb) {
+#include "gemm_tile_body.inc"
 }
 
 __global__ void gemm_splitk_reduce_kernel(const float* slabs, const float* bias, const float* res, float* y,
@@ -225,39 +167,56 @@ static size_t gemm_workspace_bytes(int M, int N, int K) {
 
 template <class Op, int BM, int BN>
 static void gemm_nt_launch(bool kv, dim3 grid, hipStream_t st, const float* x, const float* w, const float* b,
-                           const float* res, float* y, int M, int N, int K, int act, int kts) {
-  if (kv)
+                           const float* res, float* y, int M, int N, int K, int act, int kts, int lda, int ldb) {
+  if constexpr (Op::A_T || Op::B_T) {
+    if (kv)
+      hipLaunchKernelGGL((gemm_ld_kernel<Op, BM, BN, true>), grid, dim3(256), 0, st, x, w, b, res, y, M, N, K, act,
+                         kts, lda, ldb);
+    else
+      hipLaunchKernelGGL((gemm_ld_kernel<Op, BM, BN, false>), grid, dim3(256), 0, st, x, w, b, res, y, M, N, K, act,
+                         kts, lda, ldb);
+  } else if (kv)
     hipLaunchKernelGGL((gemm_nt_kernel<Op, BM, BN, true>), grid, dim3(256), 0, st, x, w, b, res, y, M, N, K, act, kts);
   else
     hipLaunchKernelGGL((gemm_nt_kernel<Op, BM, BN, false>), grid, dim3(256), 0, st, x, w, b, res, y, M, N, K, act, kts);
 }
 
 // Tile choice and split-K of both arms, every M >= 1.  A missing or short workspace runs the unsplit 64x64 kernel.
+// kv: every operand can take 16-byte loads (the caller knows the operand forms).
 template <class Op>
 static int gemm_nt_mfma(const float* x, const float* w, const float* b, const float* res, float* y, int M, int N,
-                        int K, int act, hipStream_t st, void* workspace, size_t ws_bytes) {
+                        int K, int act, hipStream_t st, void* workspace, size_t ws_bytes, bool kv, int lda = 0,
+                        int ldb = 0) {
   // fewer than one 128x128 tile per CU: 64x64 tiles (4x the blocks) keep the chip busy
   const long long t128 = (long long)((M + 127) / 128) * ((N + 127) / 128);
-  const bool kv = (K & 3) == 0 && ((((uintptr_t)x | (uintptr_t)w)) & 15) == 0;
   const dim3 g64((N + 63) / 64, (M + 63) / 64);
   const int S = workspace && t128 < 256 ? gemm_split(M, N, K) : 1;
   if (t128 >= 256) {
-    gemm_nt_launch<Op, 128, 128>(kv, dim3((N + 127) / 128, (M + 127) / 128), st, x, w, b, res, y, M, N, K, act, 0);
+    gemm_nt_launch<Op, 128, 128>(kv, dim3((N + 127) / 128, (M + 127) / 128), st, x, w, b, res, y, M, N, K, act, 0,
+                                 lda, ldb);
   } else if (S > 1 && ws_bytes >= (size_t)S * M * N * sizeof(float)) {
     const int nk = (K + GM_BK - 1) / GM_BK;
     const int kts = (nk + S - 1) / S;
     const int Se = (nk + kts - 1) / kts;  // slices that own at least one k-tile
     gemm_nt_launch<Op, 64, 64>(kv, dim3(g64.x, g64.y, Se), st, x, w, nullptr, nullptr, (float*)workspace, M, N, K, 0,
-                               kts);
+                               kts, lda, ldb);
     const long long MN = (long long)M * N;
     const unsigned grid = MN > 4096 * 256 ? 4096 : (unsigned)((MN + 255) / 256);
     hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(grid), dim3(256), 0, st, (const float*)workspace, b, res, y, MN,
                        N, Se, act);
   } else {
-    gemm_nt_launch<Op, 64, 64>(kv, g64, st, x, w, b, res, y, M, N, K, act, 0);
+    gemm_nt_launch<Op, 64, 64>(kv, g64, st, x, w, b, res, y, M, N, K, act, 0, lda, ldb);
   }
   VS_CHECK_LAUNCH();
   return VS_OK;
+}
+
+// both operands K-contiguous
+template <class Op>
+static int gemm_nt_mfma(const float* x, const float* w, const float* b, const float* res, float* y, int M, int N,
+                        int K, int act, hipStream_t st, void* workspace, size_t ws_bytes) {
+  const bool kv = (K & 3) == 0 && ((((uintptr_t)x | (uintptr_t)w)) & 15) == 0;
+  return gemm_nt_mfma<Op>(x, w, b, res, y, M, N, K, act, st, workspace, ws_bytes, kv);
 }
 
 // the fp32 arm above 64 rows, for vs_gemm_nt_f32 (txenc_ops.hip)
@@ -290,4 +249,36 @@ extern "C" int vs_gemm_nt_bf16_ws(const float* x, const float* w, const float* b
   VS_CHECK_ARG(x && w && y && M > 0 && N > 0 && K > 0, "bad args");
   VS_CHECK_ARG(act >= 0 && act <= 2, "act must be 0 (none), 1 (relu) or 2 (gelu_new)");
   return gemm_nt_mfma<GemmBf16>(x, w, b, res, y, M, N, K, act, (hipStream_t)stream, workspace, ws_bytes);
+}
+
+/* vs_gemm_nt_bf16_ws with either operand K-strided, as a row range of an array of lda / ldb rows (vidsitu_hip.h). */
+extern "C" int vs_gemm_bf16_ld_ws(const float* a, const float* b, const float* bias, const float* res, float* y, int M,
+                                  int N, int K, int a_kstrided, int b_kstrided, int lda, int ldb, int act,
+                                  void* workspace, size_t ws_bytes, void* stream) {
+  VS_CHECK_ARG(a && b && y && M > 0 && N > 0 && K > 0, "bad args");
+  VS_CHECK_ARG(act >= 0 && act <= 2, "act must be 0 (none), 1 (relu) or 2 (gelu_new)");
+  VS_CHECK_ARG((a_kstrided | b_kstrided | 1) == 1, "a_kstrided and b_kstrided must be 0 or 1");
+  VS_CHECK_ARG((!a_kstrided || lda >= M) && (!b_kstrided || ldb >= N),
+               "the leading dimension of a K-strided operand is at least its row count");
+  const size_t need = gemm_workspace_bytes(M, N, K);
+  VS_CHECK_ARG(!need || (workspace && ws_bytes >= need), "workspace shorter than vs_gemm_nt_bf16_workspace_bytes");
+  hipStream_t st = (hipStream_t)stream;
+  if (!a_kstrided && !b_kstrided)
+    return gemm_nt_mfma<GemmBf16>(a, b, bias, res, y, M, N, K, act, st, workspace, ws_bytes);
+  // 16-byte loads run along an operand's contiguous axis: K, or the rows of a strided operand (whole row quads)
+  const bool kv = ((((uintptr_t)a | (uintptr_t)b)) & 15) == 0 && ((a_kstrided ? M | lda : K) & 3) == 0 &&
+                  ((b_kstrided ? N | ldb : K) & 3) == 0;
+  if (!a_kstrided)
+    return gemm_nt_mfma<GemmBf16T<false, true>>(a, b, bias, res, y, M, N, K, act, st, workspace, ws_bytes, kv, 0, ldb);
+  if (!b_kstrided)
+    return gemm_nt_mfma<GemmBf16T<true, false>>(a, b, bias, res, y, M, N, K, act, st, workspace, ws_bytes, kv, lda, 0);
+  return gemm_nt_mfma<GemmBf16T<true, true>>(a, b, bias, res, y, M, N, K, act, st, workspace, ws_bytes, kv, lda, ldb);
+}
+
+/* The same with whole arrays: lda = M, ldb = N. */
+extern "C" int vs_gemm_bf16_ws(const float* a, const float* b, const float* bias, const float* res, float* y, int M,
+                               int N, int K, int a_kstrided, int b_kstrided, int act, void* workspace,
+                               size_t ws_bytes, void* stream) {
+  return vs_gemm_bf16_ld_ws(a, b, bias, res, y, M, N, K, a_kstrided, b_kstrided, M, N, act, workspace, ws_bytes,
+                            stream);
 }

@@ -161,6 +161,7 @@ class CfgProcessor:
         cfg.mdl.setdefault("gpt2_dropout", 0.0)
         cfg.mdl.setdefault("gpt2_matmul", "fp32")
         cfg.mdl.setdefault("rob_dropout", 0.0)
+        cfg.mdl.setdefault("rob_matmul", "fp32")
         return cfg
 
     @staticmethod

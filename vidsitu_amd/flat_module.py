@@ -139,17 +139,23 @@ class FlatParamModule(nn.Module):
             self._drop_state.copy_(new)
 
     # ---- backward of a dense layer ---------------------------------------------------------------------
-    def _linear_bwd(self, name, x, dy, bias=True, need_dx=True, conv1d=False, bf16=False):
+    def _linear_bwd(self, name, x, dy, bias=True, need_dx=True, conv1d=False, bf16=False, direct=False):
         """y = x W^T + b with W [out, in]: dW = dy^T x, db = colsum(dy), dx = dy W.  conv1d: huggingface's Conv1D,
         y = x W + b with W [in, out]: dW = x^T dy, and the parameter itself is the K-contiguous operand of dx.  bf16: both
-        GEMMs take bf16 operands (ops.gemm_nt); the bias gradient stays an fp32 column sum."""
+        GEMMs take bf16 operands (ops.gemm_nt); the bias gradient stays an fp32 column sum.  direct: bf16 operands
+        through the K-strided forms of ops.gemm_bf16, which read dy, x and W where they lie: no transposed copy."""
         w = self.P(name + ".weight")
         a, b = (x, dy) if conv1d else (dy, x)
-        ops.gemm_nt(ops.transpose_f32(a), ops.transpose_f32(b), out=self._grad(name + ".weight"), bf16=bf16)
+        if direct:
+            ops.gemm_bf16(a, b, out=self._grad(name + ".weight"), a_t=True, b_t=True)
+        else:
+            ops.gemm_nt(ops.transpose_f32(a), ops.transpose_f32(b), out=self._grad(name + ".weight"), bf16=bf16)
         if bias:
             ops.colsum_f32(dy, out=self._grad(name + ".bias"))
         if not need_dx:
             return None
+        if direct:
+            return ops.gemm_bf16(dy, w, b_t=not conv1d)
         return ops.gemm_nt(dy, w if conv1d else ops.transpose_f32(w), bf16=bf16)
 
     # ---- hand-over of the saved activations ------------------------------------------------------------

@@ -25,6 +25,14 @@ and never advance the state; at every probability 0 the model issues the launche
 Training: `forward_train` keeps the activations, `backward` is a manual HIP backward behind ONE autograd node
 (`roberta_apply` -> `flat_module.FlatTrainFn`); parameter gradients are written with overwrite semantics.  Flat
 registration, the state-dict rules, the fused q/k/v cache's life and the dense-layer backward are `FlatParamModule`'s.
+
+`matmul="bf16"` (`mdl.rob_matmul`): the encoder's dense layers -- the fused q/k/v projection, `attention.output.dense`,
+`intermediate.dense`, `output.dense` -- take bf16 operands with fp32 accumulation, in training and in the plain forward
+alike.  Activations and weights stay fp32 in memory and are rounded inside the GEMM's loader.  The backward's products
+go through `ops.gemm_bf16`, whose K-strided operand forms read dy, x and W where they lie: no transposed copy of any
+of them exists in that mode, and the cached transposed q/k/v weight is not built.  Parameters, Adam, the embeddings,
+LayerNorm, attention, GELU, dropout, bias gradients, the pooler and the classification head (a handful of rows) stay
+fp32.  The default "fp32" issues the launches it issued before the argument existed.
 """
 import torch
 from torch import nn
@@ -45,13 +53,19 @@ class _RobertaHip(FlatParamModule):
     """Parameters under huggingface's names, the encoder's forward / backward."""
 
     PREFIX = ""
-    _CACHES = ("_qkv",)  # layer -> ([3D][D] weight, [3D] bias, [D][3D] transposed weight): one GEMM for q, k and v
+    # layer -> ([3D][D] weight, [3D] bias, [D][3D] transposed weight | None in bf16 mode): one GEMM for q, k and v
+    _CACHES = ("_qkv",)
     _CAPTURE_MSG = "RoBERTa's fused q/k/v weights must exist before a graph capture (run one eager step first)"
     _DROP_CAPTURE_MSG = "the RoBERTa dropout state must exist before a graph capture (run one eager step first)"
 
     def __init__(self, n_layer, d_model, n_head, n_positions, vocab_size, d_ffn, pad_token_id=1, layer_norm_eps=1e-5,
-                 add_pooling_layer=True, num_labels=0, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0):
+                 add_pooling_layer=True, num_labels=0, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0,
+                 matmul="fp32"):
         super().__init__()
+        if matmul not in ("fp32", "bf16"):
+            raise ValueError(f"matmul must be 'fp32' or 'bf16', got {matmul!r}")
+        self.matmul = matmul
+        self._bf16 = matmul == "bf16"  # the encoder's dense layers only
         if d_model % n_head:
             raise ValueError("d_model must be a multiple of n_head")
         self.hidden_dropout_prob = float(hidden_dropout_prob)
@@ -121,7 +135,7 @@ class _RobertaHip(FlatParamModule):
         def make():
             w = torch.cat([self.E(q + s + ".weight").detach() for s in ("query", "key", "value")], 0).contiguous()
             b = torch.cat([self.E(q + s + ".bias").detach() for s in ("query", "key", "value")], 0).contiguous()
-            return w, b, ops.transpose_f32(w)
+            return w, b, None if self._bf16 else ops.transpose_f32(w)  # bf16: dx reads w itself (K-strided)
 
         return self._copy(self._qkv, i, self.E(q + "query.weight"), make)
 
@@ -139,6 +153,13 @@ class _RobertaHip(FlatParamModule):
 
     def _dense(self, name, x):
         return ops.gemm_nt(x, self.E(name + ".weight"), self.E(name + ".bias"))
+
+    def _enc_dense(self, name, x):
+        """A dense layer of the encoder stack: the one place `matmul` acts in the forward (beside the fused q/k/v)."""
+        return ops.gemm_nt(x, self.E(name + ".weight"), self.E(name + ".bias"), bf16=self._bf16)
+
+    def _enc_linear_bwd(self, name, x, dy):
+        return self._linear_bwd(name, x, dy, direct=self._bf16)
 
     def _tick(self, tokens, keep):
         """The [seed, step] snapshot of a train-mode pass with dropout (one tick); None otherwise."""
@@ -182,14 +203,14 @@ class _RobertaHip(FlatParamModule):
         for i in range(self.n_layer):
             q = f"encoder.layer.{i}."
             w, b, _ = self._fused_qkv(i)
-            qkv = ops.gemm_nt(h, w, b)
+            qkv = ops.gemm_nt(h, w, b, bf16=self._bf16)
             ctx = ops.attn_pad(qkv, km, r, l, self.n_head, drop=self._site(snap, 1 + 3 * i, att))
-            ao = self._dense(q + "attention.output.dense", ctx)
+            ao = self._enc_dense(q + "attention.output.dense", ctx)
             ao, h1, mean1, rstd1 = self._ln_site(ao, h, q + "attention.output.LayerNorm",
                                                  self._site(snap, 2 + 3 * i, hid))
-            f_pre = self._dense(q + "intermediate.dense", h1)
+            f_pre = self._enc_dense(q + "intermediate.dense", h1)
             f = ops.gelu_erf_fwd(f_pre)
-            fo = self._dense(q + "output.dense", f)
+            fo = self._enc_dense(q + "output.dense", f)
             fo, h2, mean2, rstd2 = self._ln_site(fo, h1, q + "output.LayerNorm", self._site(snap, 3 + 3 * i, hid))
             if keep:
                 layers.append((h, qkv, ctx, ao, mean1, rstd1, h1, f_pre, f, fo, mean2, rstd2))
@@ -211,21 +232,27 @@ class _RobertaHip(FlatParamModule):
             h_in, qkv, ctx, ao, mean1, rstd1, h1, f_pre, f, fo, mean2, rstd2 = layers[i]
             ds2, dfo = self._ln_site_bwd(dh, fo, h1, q + "output.LayerNorm", mean2, rstd2,
                                          self._site(snap, 3 + 3 * i, hid))
-            df = self._linear_bwd(q + "output.dense", f, dfo)
+            df = self._enc_linear_bwd(q + "output.dense", f, dfo)
             df_pre = ops.gelu_erf_bwd(df, f_pre)
-            dh1 = ops.add_f32(self._linear_bwd(q + "intermediate.dense", h1, df_pre), ds2)
+            dh1 = ops.add_f32(self._enc_linear_bwd(q + "intermediate.dense", h1, df_pre), ds2)
             ds1, dao = self._ln_site_bwd(dh1, ao, h_in, q + "attention.output.LayerNorm", mean1, rstd1,
                                          self._site(snap, 2 + 3 * i, hid))
-            dctx = self._linear_bwd(q + "attention.output.dense", ctx, dao)
+            dctx = self._enc_linear_bwd(q + "attention.output.dense", ctx, dao)
             dqkv = ops.attn_pad_bwd(qkv, km, dctx, r, l, self.n_head, drop=self._site(snap, 1 + 3 * i, att))
             # the fused projection: weight gradients straight into the three separate parameters
-            _, _, wt = self._fused_qkv(i)
-            dqkv_t, h_t = ops.transpose_f32(dqkv), ops.transpose_f32(h_in)
+            w, _, wt = self._fused_qkv(i)
+            if not self._bf16:
+                dqkv_t, h_t = ops.transpose_f32(dqkv), ops.transpose_f32(h_in)
             db = ops.colsum_f32(dqkv)
             for s, nm in enumerate(("query", "key", "value")):
-                ops.gemm_nt(dqkv_t[s * d:(s + 1) * d], h_t, out=self._grad(q + "attention.self." + nm + ".weight"))
+                dw = self._grad(q + "attention.self." + nm + ".weight")
+                if self._bf16:  # a row range of dqkv^T is a column range of dqkv: a K-strided operand where it lies
+                    ops.gemm_bf16(dqkv[:, s * d:(s + 1) * d], h_in, out=dw, a_t=True, b_t=True)
+                else:
+                    ops.gemm_nt(dqkv_t[s * d:(s + 1) * d], h_t, out=dw)
                 self._grad(q + "attention.self." + nm + ".bias").copy_(db[s * d:(s + 1) * d])
-            dh = ops.add_f32(ops.gemm_nt(dqkv, wt), ds1)
+            dx = ops.gemm_bf16(dqkv, w, b_t=True) if self._bf16 else ops.gemm_nt(dqkv, wt)
+            dh = ops.add_f32(dx, ds1)
             layers[i] = None
         if hid is not None:
             dh = ops.dropout_add(dh, None, self._site(snap, 0, hid))

@@ -29,6 +29,11 @@ def _rob_dropout(cfg):
     return dict(hidden_dropout_prob=p, attention_probs_dropout_prob=p)
 
 
+def _rob_matmul(cfg):
+    """`mdl.rob_matmul`: 'fp32' | 'bf16', the operand precision of the RoBERTa encoder's dense layers."""
+    return dict(matmul=str(cfg.mdl.get("rob_matmul", "fp32")))
+
+
 class Simple_EvRel_Roberta(nn.Module):
     """`mdl_evrel.py:12-50` (`rob_evrel`): RoBERTa sequence classification (5 labels) over the paired SRL text
     `evrel_seq_out` [B, 4, n_ann, 120]."""
@@ -42,7 +47,7 @@ class Simple_EvRel_Roberta(nn.Module):
 
     def build_model(self):
         self.rob_mdl = hf_roberta.build(self.full_cfg.mdl.rob_mdl_name, RobertaForSequenceClassificationHip,
-                                        num_labels=5, **_rob_dropout(self.full_cfg))
+                                        num_labels=5, **_rob_dropout(self.full_cfg), **_rob_matmul(self.full_cfg))
 
     def forward(self, inp):
         src_toks, src_attn_mask, (B, num_ev, num_seq_eg) = _flat_tokens(inp["evrel_seq_out"],
@@ -68,7 +73,7 @@ class SFPret_SimpleEvRel(nn.Module):
 
     def build_model(self):
         self.rob_mdl = hf_roberta.build(self.full_cfg.mdl.rob_mdl_name, RobertaModelHip, add_pooling_layer=True,
-                                        **_rob_dropout(self.full_cfg))
+                                        **_rob_dropout(self.full_cfg), **_rob_matmul(self.full_cfg))
         head_dim = get_head_dim(self.full_cfg)
         hidden = self.rob_mdl.d_model  # 768 for roberta-base: the reference's 1792 = 1024 + 768
         self.vid_feat_encoder = HipMLP(nn.Linear(head_dim, 1024), nn.ReLU(), nn.Linear(1024, 1024))

@@ -1181,6 +1181,48 @@ def gemm_nt(x, w, b=None, res=None, act=ACT_NONE, out=None, bf16=False):
     return y
 
 
+def _kstrided(t, name):
+    """A K-strided operand [K, rows]: rows contiguous, every k one leading dimension on (a column range of a
+    contiguous array passes as it is).  -> (tensor, rows, K, leading dimension)."""
+    if t.dtype != torch.float32:
+        raise _lib.VsError("fp32 tensor expected")
+    if t.dim() != 2:
+        raise _lib.VsError(f"gemm_bf16: {name} must be 2-d, got {tuple(t.shape)}")
+    k, rows = t.shape
+    if rows > 1 and t.stride(1) != 1 or k > 1 and t.stride(0) < rows:
+        t = t.contiguous()
+    return t, rows, k, (t.stride(0) if k > 1 else rows)
+
+
+def gemm_bf16(a, b, bias=None, res=None, act=ACT_NONE, out=None, a_t=False, b_t=False):
+    """act(A @ B^T + bias) + res with bf16 operands as gemm_nt(bf16=True), A [M, K] and B [N, K]; a_t / b_t: that
+    operand is stored [K][rows] (a = A^T as a [K, M] tensor, b = B^T as [K, N]) and is transposed inside the
+    kernel's loader: bit for bit gemm_nt(transpose_f32(a), ..., bf16=True) without the copy.  A column range of a
+    contiguous array is a valid strided operand (its rows are a row range of A)."""
+    if a.dim() != 2 or b.dim() != 2:
+        raise _lib.VsError(f"gemm_bf16: 2-d operands expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if a_t:
+        a, m, k, lda = _kstrided(a, "a")
+    else:
+        a, (m, k), lda = _f32c(a), a.shape, 0
+    if b_t:
+        b, n, kb, ldb = _kstrided(b, "b")
+    else:
+        b, (n, kb), ldb = _f32c(b), b.shape, 0
+    if kb != k:
+        raise _lib.VsError(f"gemm_bf16: K mismatch {tuple(a.shape)} (a_t={bool(a_t)}) x {tuple(b.shape)} "
+                           f"(b_t={bool(b_t)})")
+    for nm, t, want in (("bias", bias, (n,)), ("res", res, (m, n)), ("out", out, (m, n))):
+        if t is not None and (tuple(t.shape) != want or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise _lib.VsError(f"gemm_bf16: {nm} must be a contiguous fp32 {want}, got {tuple(t.shape)}")
+    y = torch.empty((m, n), dtype=torch.float32, device=a.device) if out is None else out
+    need = _lib.load().vs_gemm_nt_bf16_workspace_bytes(m, n, k)
+    ws = _workspace(need, a.device) if need else None
+    _lib.call("vs_gemm_bf16_ld_ws", _ptr(a), _ptr(b), _ptr(bias), _ptr(res), _ptr(y), m, n, k, int(bool(a_t)),
+              int(bool(b_t)), int(lda), int(ldb), int(act), _ptr(ws), C.c_size_t(ws.numel() if need else 0), _stream())
+    return y
+
+
 _RESIZE_TABLES = {}
 
 

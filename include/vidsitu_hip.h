@@ -745,6 +745,33 @@ int vs_beam_step(const float* row_val, const int64_t* row_idx, const int64_t* to
                  int k, int V, int step, int max_len, int eos, int normalize, float len_penalty,
                  void* stream);
 
+/* ---- Sampling search (fairseq search.Sampling restated; docs/beam_search_parity.md, "Sampling").
+ * vs_sample_token draws ONE token per row of a search step.  lp_j follows the rules of vs_beam_topk[_ngram]
+ * (same arguments; ngram == 0: no ban, tokens may be NULL); p_j = exp(lp_j) is not renormalised.  Kept set, tokens
+ * ranked by (lp descending, token ascending): topk > 0 keeps the first min(topk, V); 0 < topp <= 1 keeps the ranked
+ * prefix up to and including the token at which the cumulative p reaches topp; neither (topk <= 0, topp <= 0) keeps
+ * every token; both are refused.  Draw: u = (w + 0.5) * 2^-32 with w the generator word (csrc/dropout_rng.h) of
+ * element row_ids[r] (NULL: r) at snap = [seed, step] and site VS_SAMPLE_SITE; the token is the inverse CDF at u * S
+ * over the kept set in ascending token id, S the kept mass.  out_val[r] = lp_token + cum[r], out_idx[r] = token; a row
+ * of kept mass 0 gives (-inf, 0).  Masses are summed as integers (p / p_max * 2^40, rounded, p_max the row's largest p
+ * after the rules): the result does not depend on any order of summation and is the same with and without a workspace.  With a workspace and V > 2048 the row is cut
+ * into slices (grid = slices x rows); without one a block per row walks the slices (V <= 65536). */
+#define VS_SAMPLE_SITE 0x53414D50u
+size_t vs_sample_token_workspace_bytes(int rows, int V);
+int vs_sample_token(const float* logits, const float* cum, const int64_t* forced, const int64_t* tokens,
+                    int tok_ld, int step, int ngram, const int64_t* snap, const int64_t* row_ids,
+                    float* out_val, int64_t* out_idx, int rows, int V, int topk, double topp, int pad, int eos,
+                    int unk, float unk_penalty, float temperature, int flags, void* workspace, size_t ws_bytes,
+                    void* stream);
+/* vs_beam_step for a sampling search: row_val / row_idx hold ONE entry per row (vs_sample_token); candidate c of a
+ * sentence is (parent beam c, row c's draw) -- no merge across beams, no sorting, at step 0 included.  Everything from
+ * finalize_hypos on is vs_beam_step's code with beam candidates per sentence. */
+int vs_sample_step(const float* row_val, const int64_t* row_idx, const int64_t* tok_in, int64_t* tok_out,
+                   const float* sc_in, float* sc_out, uint8_t* ignore, uint8_t* finished, int* nfin,
+                   int* remaining, int64_t* fin_tok, float* fin_score, float* fin_pos, int* fin_len,
+                   int64_t* reorder, const int32_t* anc_in, int32_t* anc_out, int anc_ld, int bsz, int beam,
+                   int step, int max_len, int eos, int normalize, float len_penalty, void* stream);
+
 /* Non-local block pieces (slowfast nonlocal_helper.Nonlocal of the i3d_r50_nl_8x8 feature model,
  * Kinetics_c2_I3D_NLN_8x8_R50.yaml:25-28): MaxPool3d([1,2,2], stride [1,2,2]) of a channels-last bf16
  * activation [NT][H][W][C] with a byte argmax per element (0..3 = (dh, dw), first maximum wins) and its

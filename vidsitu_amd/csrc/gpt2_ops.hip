@@ -7,6 +7,7 @@
 #include <math.h>
 
 #include "attn_shared.h"
+#include "beam_shared.h"
 #include "common.h"
 #include "dropout_rng.h"
 
@@ -383,25 +384,6 @@ __device__ __forceinline__ bool bt_better(float v, int i, float w, int j) {
   return v > w || (v == w && i < j);
 }
 
-// Sets bit t - base of bm for every banned token t in [base, base + nbits) of one row: threads stride
-// over the start positions i of the earlier n-1-grams, n-1 compares each against the suffix
-// row[step+2-n .. step]; the follower row[i+n-1] lies at or before `step` -- nothing after it is read
-// (the tail of the search's token buffer is uninitialised).  step + 2 - n < 0: no start position,
-// nothing banned (:756).  The caller zeroes bm and syncs before, and syncs after; a set has no order.
-__device__ __forceinline__ void bt_mark_banned(const int64_t* row, int step, int n, int base, int nbits,
-                                               int V, unsigned* bm, int tid) {
-  const int s0 = step + 2 - n;
-  for (int i = tid; i < s0; i += 256) {
-    bool eq = true;
-    for (int j = 0; j < n - 1 && eq; ++j) eq = row[i + j] == row[s0 + j];
-    if (!eq) continue;
-    const long long t = row[i + n - 1];
-    if (t < base || t >= V || t - base >= nbits) continue;
-    const int o = (int)(t - base);
-    atomicOr(&bm[o >> 5], 1u << (o & 31));
-  }
-}
-
 template <bool BAN>
 __global__ __launch_bounds__(256) void beam_topk_kernel(const float* logits, const float* cum,
                                                         const int64_t* forced, const int64_t* tokens,
@@ -440,22 +422,10 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* logits, con
   }
   const float lse = mx + logf(red[0]);
   const float add = cum ? cum[r] : 0.f;
-  const long long f = forced ? forced[r] : -1;
-  const bool force = f >= 0 && f != pad;
+  const BtRules R = bt_rules(forced, r, pad, eos, unk, unk_penalty, inv_temp, flags, lse);
 
   auto score = [&](int j) {
-    float lp = x[j] * inv_temp - lse;
-    if (lp != lp) lp = -INFINITY;
-    if (j == pad) lp = -INFINITY;
-    if (j == unk) lp -= unk_penalty;
-    if ((flags & 1) && j != eos) lp = -INFINITY;
-    if (force) {
-      if (j != (int)f) lp = -INFINITY;
-    } else if ((flags & 2) && j == eos) {
-      lp = -INFINITY;
-    }
-    if (BAN && ((bt_bm[j >> 5] >> (j & 31)) & 1u)) lp = -INFINITY;
-    return lp + add;
+    return bt_rule_lp(R, x[j], j, BAN && ((bt_bm[j >> 5] >> (j & 31)) & 1u)) + add;
   };
   // k rounds of a block-wide argmax; each round every thread rescans its slice for its best
   // candidate that is worse than the previous winner (value, index order) -- k <= 2*beam is small
@@ -498,42 +468,6 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* logits, con
 //   1. per slice: max and sum exp      2. per slice: the row's lse from the partials (fixed order,
 //   the same bits in every block), exact scores of the slice in registers, k rounds of block argmax
 //   3. per row: merge slices x k candidates.  Same (value desc, token asc) order as the one-block kernel.
-#define BT_SLICE 2048
-#define BT_E (BT_SLICE / 256)
-
-__global__ __launch_bounds__(256) void beam_lse_part_kernel(const float* logits, float2* part, int V,
-                                                            float inv_temp) {
-  __shared__ float red[4];
-  const int sl = blockIdx.x, r = blockIdx.y, tid = threadIdx.x, S = gridDim.x;
-  const float* x = logits + (long long)r * V;
-  float v[BT_E];
-  float mx = -INFINITY;
-#pragma unroll
-  for (int e = 0; e < BT_E; ++e) {
-    const int j = sl * BT_SLICE + e * 256 + tid;
-    const bool ok = j < V;
-    const float t = x[ok ? j : 0] * inv_temp;
-    v[e] = ok ? t : -INFINITY;
-    mx = fmaxf(mx, v[e]);
-  }
-  mx = wave_reduce_max(mx);
-  if ((tid & 63) == 0) red[tid >> 6] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  __syncthreads();
-  float sum = 0.f;
-#pragma unroll
-  for (int e = 0; e < BT_E; ++e) {
-    const int j = sl * BT_SLICE + e * 256 + tid;
-    // a -inf logit adds exactly 0; written out so that a slice of nothing but -inf (mx = -inf) gives 0 and
-    // not exp(-inf - -inf) = NaN, which would turn the whole row into -inf (a NaN logit still does)
-    if (j < V) sum += v[e] == -INFINITY ? 0.f : expf(v[e] - mx);
-  }
-  sum = wave_reduce_sum(sum);
-  if ((tid & 63) == 0) red[tid >> 6] = sum;
-  __syncthreads();
-  if (tid == 0) part[(long long)r * S + sl] = make_float2(mx, (red[0] + red[1]) + (red[2] + red[3]));
-}
 
 __device__ __forceinline__ void bt_block_argbest(float& bv, int& bi, float* cv, int* ci, int tid) {
 #pragma unroll
@@ -577,34 +511,16 @@ __global__ __launch_bounds__(256) void beam_topk_part_kernel(
     bt_mark_banned(tokens + (long long)r * tok_ld, step, ngram, sl * BT_SLICE, BT_SLICE, V, bm, tid);
     __syncthreads();
   }
-  float M = -INFINITY;
-  for (int q = 0; q < S; ++q) M = fmaxf(M, part[(long long)r * S + q].x);
-  float sum = 0.f;
-  for (int q = 0; q < S; ++q) {
-    const float2 pq = part[(long long)r * S + q];
-    sum += pq.y * expf(pq.x - M);
-  }
-  const float lse = M + logf(sum);
+  const float lse = bt_lse_combine(part + (long long)r * S, S);
   const float add = cum ? cum[r] : 0.f;
-  const long long f = forced ? forced[r] : -1;
-  const bool force = f >= 0 && f != pad;
+  const BtRules R = bt_rules(forced, r, pad, eos, unk, unk_penalty, inv_temp, flags, lse);
   float v[BT_E];
   int idx[BT_E];
 #pragma unroll
   for (int e = 0; e < BT_E; ++e) {
     const int j = sl * BT_SLICE + e * 256 + tid;
     const bool ok = j < V;
-    float lp = x[ok ? j : 0] * inv_temp - lse;
-    if (lp != lp) lp = -INFINITY;
-    if (j == pad) lp = -INFINITY;
-    if (j == unk) lp -= unk_penalty;
-    if ((flags & 1) && j != eos) lp = -INFINITY;
-    if (force) {
-      if (j != (int)f) lp = -INFINITY;
-    } else if ((flags & 2) && j == eos) {
-      lp = -INFINITY;
-    }
-    if (BAN && ((bm[(e * 256 + tid) >> 5] >> (tid & 31)) & 1u)) lp = -INFINITY;
+    const float lp = bt_rule_lp(R, x[ok ? j : 0], j, BAN && ((bm[(e * 256 + tid) >> 5] >> (tid & 31)) & 1u));
     v[e] = ok ? lp + add : -INFINITY;
     idx[e] = ok ? j : 0x7fffffff;
   }
@@ -668,9 +584,6 @@ __global__ __launch_bounds__(256) void beam_topk_merge_kernel(const float* cand_
     }
   }
 }
-
-static inline int bt_slices(int V) { return (V + BT_SLICE - 1) / BT_SLICE; }
-static inline size_t bt_bitmap_bytes(int V) { return (((size_t)V + 31) / 32) * 4; }  // one-block ban bitmap
 
 extern "C" size_t vs_beam_topk_workspace_bytes(int rows, int V, int k) {
   const size_t S = (size_t)bt_slices(V);
@@ -1189,37 +1102,6 @@ extern "C" int vs_xent_ignore_grad_dev(const float* logits, const int64_t* label
 // step, one block per sentence, no host synchronisation.  Finished sentences are not removed from
 // the batch (the reference shrinks it); their rows idle, results are unchanged.
 // =============================================================================================
-struct BeamStepP {
-  const float* row_val;     // [bsz*beam][k]   per-row top-k of vs_beam_topk (cumulative scores added)
-  const int64_t* row_idx;   // [bsz*beam][k]
-  const int64_t* tok_in;    // [bsz*beam][Lt]  Lt = max_len + 2
-  int64_t* tok_out;
-  const float* sc_in;       // [bsz*beam][Ls]  Ls = max_len + 1
-  float* sc_out;
-  uint8_t* ignore;          // [bsz][beam]     cands_to_ignore
-  uint8_t* finished;        // [bsz]
-  int* nfin;                // [bsz]           hypotheses finalized so far
-  int* remaining;           // [1]             sentences not finished yet
-  int64_t* fin_tok;         // [bsz][beam][Ls] finalized token sequences (eos included)
-  float* fin_score;         // [bsz][beam]
-  float* fin_pos;           // [bsz][beam][Ls] positional scores
-  int* fin_len;             // [bsz][beam]
-  int64_t* reorder;         // [bsz*beam]      parent row of every new row (KV-cache gather index)
-  const int* anc_in;        // [bsz*beam][anc_ld] or NULL: cache row holding position j of the hypothesis
-  int* anc_out;             //                  (vs_attn_decode's ancestry table; replaces the gather)
-  int anc_ld;
-  int beam, k, V, step, max_len, Lt, Ls, eos, normalize;
-  float len_penalty;
-};
-
-#define BS_MAXC 64  // 2 * beam candidates kept per sentence (beam <= 32)
-
-__device__ __forceinline__ void bs_anc_row(const BeamStepP& p, long long nrow, long long prow, int lane) {
-  if (!p.anc_out) return;
-  for (int j = lane; j <= p.step + 1 && j < p.anc_ld; j += 64)
-    p.anc_out[nrow * p.anc_ld + j] = j <= p.step ? p.anc_in[prow * p.anc_ld + j] : (int)nrow;
-}
-
 __global__ __launch_bounds__(64) void beam_step_kernel(BeamStepP p) {
   __shared__ float cv[BS_MAXC];      // merged candidates: value
   __shared__ int ct[BS_MAXC];        //                    token
@@ -1233,12 +1115,7 @@ __global__ __launch_bounds__(64) void beam_step_kernel(BeamStepP p) {
   const int beam = p.beam, k = p.k, csz = 2 * beam;
   const long long row0 = (long long)s * beam;
   if (p.finished[s]) {  // idle rows: carry the state over unchanged
-    for (int b = 0; b < beam; ++b) {
-      for (int j = lane; j < p.Lt; j += 64) p.tok_out[(row0 + b) * p.Lt + j] = p.tok_in[(row0 + b) * p.Lt + j];
-      for (int j = lane; j < p.Ls; j += 64) p.sc_out[(row0 + b) * p.Ls + j] = p.sc_in[(row0 + b) * p.Ls + j];
-      if (lane == 0) p.reorder[row0 + b] = row0 + b;
-      bs_anc_row(p, row0 + b, row0 + b, lane);
-    }
+    bs_idle_rows(p, row0, lane);
     return;
   }
   // ---- fairseq BeamSearch.step on the per-row lists: the csz best of beam*k entries, by value
@@ -1281,84 +1158,7 @@ __global__ __launch_bounds__(64) void beam_step_kernel(BeamStepP p) {
     pv = bestv[0]; pf = bestf[0];
     __syncthreads();
   }
-  // ---- finalize hypotheses that end in eos among the first `beam` candidates (lane 0: in order)
-  if (lane == 0) {
-    int seen = 0;
-    for (int c = 0; c < beam; ++c) {
-      const bool is_eos = ct[c] == p.eos && cv[c] != -INFINITY && !p.ignore[s * beam + c];
-      if (!is_eos) continue;
-      seen = 1;
-      if (p.nfin[s] < beam) {
-        const int h = p.nfin[s]++;
-        const long long prow = row0 + cb[c];
-        int64_t* ft = p.fin_tok + ((long long)s * beam + h) * p.Ls;
-        float* fp = p.fin_pos + ((long long)s * beam + h) * p.Ls;
-        for (int j = 0; j < p.step; ++j) ft[j] = p.tok_in[prow * p.Lt + 1 + j];
-        ft[p.step] = p.eos;
-        float prev = 0.f;
-        for (int j = 0; j < p.step; ++j) {
-          const float cur = p.sc_in[prow * p.Ls + j];
-          fp[j] = j == 0 ? cur : cur - prev;
-          prev = cur;
-        }
-        fp[p.step] = p.step == 0 ? cv[c] : cv[c] - prev;
-        float sc = cv[c];
-        if (p.normalize) {
-          // the reference divides by the correctly rounded power; powf is 1 ulp off for some lengths even
-          // where the power is exact (41^1), so the exact cases -- 1 is the default -- do not go through it
-          const float len = (float)(p.step + 1);
-          sc = sc / (p.len_penalty == 1.f ? len : p.len_penalty == 0.f ? 1.f : powf(len, p.len_penalty));
-        }
-        p.fin_score[s * beam + h] = sc;
-        p.fin_len[s * beam + h] = p.step + 1;
-      }
-    }
-    int fin_now = 0;
-    if (seen && (p.nfin[s] == beam || p.step == p.max_len)) {
-      p.finished[s] = 1;
-      atomicSub(p.remaining, 1);
-      fin_now = 1;
-    }
-    sh_new_fin = fin_now;
-  }
-  __syncthreads();
-  if (sh_new_fin) {
-    for (int b = 0; b < beam; ++b) {
-      for (int j = lane; j < p.Lt; j += 64) p.tok_out[(row0 + b) * p.Lt + j] = p.tok_in[(row0 + b) * p.Lt + j];
-      for (int j = lane; j < p.Ls; j += 64) p.sc_out[(row0 + b) * p.Ls + j] = p.sc_in[(row0 + b) * p.Ls + j];
-      if (lane == 0) p.reorder[row0 + b] = row0 + b;
-      bs_anc_row(p, row0 + b, row0 + b, lane);
-    }
-    return;
-  }
-  // ---- the `beam` live candidates with the smallest rank (eos / ignored ones sort behind)
-  if (lane == 0) {
-    int n = 0;
-    for (int pass = 0; pass < 2 && n < beam; ++pass)
-      for (int c = 0; c < ncand && n < beam; ++c) {
-        bool dead = ct[c] == p.eos && cv[c] != -INFINITY;
-        if (c < beam) dead = dead || p.ignore[s * beam + c];
-        if ((pass == 0) == !dead) act[n++] = c | (dead ? 0x10000 : 0);
-      }
-    for (int b = 0; b < beam; ++b) p.ignore[s * beam + b] = (act[b] & 0x10000) ? 1 : 0;
-  }
-  __syncthreads();
-  for (int b = 0; b < beam; ++b) {
-    const int c = act[b] & 0xffff;
-    const long long prow = row0 + cb[c], nrow = row0 + b;
-    for (int j = lane; j < p.Lt; j += 64) {
-      int64_t t = p.tok_in[prow * p.Lt + j];
-      if (j == p.step + 1) t = ct[c];
-      p.tok_out[nrow * p.Lt + j] = t;
-    }
-    for (int j = lane; j < p.Ls; j += 64) {
-      float v = p.sc_in[prow * p.Ls + j];
-      if (j == p.step) v = cv[c];
-      p.sc_out[nrow * p.Ls + j] = v;
-    }
-    if (lane == 0) p.reorder[nrow] = prow;
-    bs_anc_row(p, nrow, prow, lane);
-  }
+  bs_finish_step(p, s, lane, ncand, cv, ct, cb, act, &sh_new_fin);
 }
 
 extern "C" int vs_beam_step(const float* row_val, const int64_t* row_idx, const int64_t* tok_in,
@@ -1372,15 +1172,9 @@ extern "C" int vs_beam_step(const float* row_val, const int64_t* row_idx, const 
                    remaining && fin_tok && fin_score && fin_pos && fin_len && reorder, "null argument");
   VS_CHECK_ARG(bsz > 0 && beam >= 1 && 2 * beam <= BS_MAXC && k >= 1 && k <= 2 * beam, "beam <= 32, k <= 2*beam");
   VS_CHECK_ARG((anc_in == nullptr) == (anc_out == nullptr) && (!anc_out || anc_ld > step), "ancestry tables");
-  BeamStepP p;
-  p.anc_in = anc_in; p.anc_out = anc_out; p.anc_ld = anc_ld;
-  p.row_val = row_val; p.row_idx = row_idx; p.tok_in = tok_in; p.tok_out = tok_out;
-  p.sc_in = sc_in; p.sc_out = sc_out; p.ignore = ignore; p.finished = finished; p.nfin = nfin;
-  p.remaining = remaining; p.fin_tok = fin_tok; p.fin_score = fin_score; p.fin_pos = fin_pos;
-  p.fin_len = fin_len; p.reorder = reorder;
-  p.beam = beam; p.k = k; p.V = V; p.step = step; p.max_len = max_len;
-  p.Lt = max_len + 2; p.Ls = max_len + 1; p.eos = eos; p.normalize = normalize;
-  p.len_penalty = len_penalty;
+  const BeamStepP p = bs_params(row_val, row_idx, tok_in, tok_out, sc_in, sc_out, ignore, finished, nfin, remaining,
+                                fin_tok, fin_score, fin_pos, fin_len, reorder, anc_in, anc_out, anc_ld, beam, k, V,
+                                step, max_len, eos, normalize, len_penalty);
   hipLaunchKernelGGL(beam_step_kernel, dim3(bsz), dim3(64), 0, (hipStream_t)stream, p);
   VS_CHECK_LAUNCH();
   return VS_OK;

@@ -1372,11 +1372,15 @@ def dropout_mask_host(seed, step, site, e0, n, thr):
     return keep
 
 
-def dropout_tick(state):
-    """state i64 [seed, step] (device) -> a new snapshot of it; the state's step advances by one."""
+def dropout_tick(state, out=None):
+    """state i64 [seed, step] (device) -> a new snapshot of it (written to `out` if given); the state's step advances
+    by one."""
     if state.dtype != torch.int64 or state.numel() != 2 or not state.is_contiguous():
         raise _lib.VsError("dropout_tick: state must be a contiguous int64 [2] tensor")
-    snap = torch.empty_like(state)
+    if out is not None and (out.dtype != torch.int64 or out.numel() != 2 or not out.is_contiguous()
+                            or out.data_ptr() == state.data_ptr()):
+        raise _lib.VsError("dropout_tick: out must be another contiguous int64 [2] tensor")
+    snap = torch.empty_like(state) if out is None else out
     _lib.call("vs_dropout_tick", _ptr(state), _ptr(snap), _stream())
     return snap
 
@@ -1501,6 +1505,56 @@ def beam_topk(logits, cum, forced, k, pad, eos, unk, unk_penalty=0.0, temperatur
               int(step), int(no_repeat_ngram_size), _ptr(val), _ptr(idx), rows, v, int(k), int(pad), int(eos),
               int(unk), float(unk_penalty), float(temperature), flags, _ptr(ws), ws.numel(), _stream())
     return val, idx
+
+
+SAMPLE_SITE = 0x53414D50  # VS_SAMPLE_SITE: the generator site of the sampling search's draws
+
+
+def sample_token(logits, cum, forced, snap, pad, eos, unk, sampling_topk=-1, sampling_topp=-1.0, unk_penalty=0.0,
+                 temperature=1.0, eos_only=False, ban_eos=False, tokens=None, step=0, no_repeat_ngram_size=0,
+                 row_ids=None, one_block=False):
+    """One drawn (value, token) per row of a sampling-search step (vs_sample_token): the scoring rules of
+    `beam_topk`, the kept set of `sampling_topk` / `sampling_topp` (neither: every token), and the inverse CDF at
+    u = (w + 0.5) * 2^-32, w the generator word of element row_ids[r] (None: r) at `snap` = int64 [seed, step] and
+    site SAMPLE_SITE.  one_block: no workspace, one block per row whatever V (same results, bit for bit)."""
+    logits = _f32c(logits)
+    rows, v = logits.shape
+    if snap.dtype != torch.int64 or snap.numel() != 2 or not snap.is_contiguous():
+        raise _lib.VsError("sample_token: snap must be a contiguous int64 [2] tensor")
+    if row_ids is not None and (row_ids.dtype != torch.int64 or row_ids.numel() != rows
+                                or not row_ids.is_contiguous()):
+        raise _lib.VsError("sample_token: row_ids must be a contiguous int64 [rows] tensor")
+    ngram = int(no_repeat_ngram_size)
+    if ngram:
+        if (tokens is None or tokens.dtype != torch.int64 or tokens.dim() != 2 or tokens.shape[0] != rows
+                or tokens.stride(1) != 1 or tokens.device != logits.device):
+            raise _lib.VsError("sample_token: no_repeat_ngram_size needs int64 tokens [rows, len] with unit inner stride")
+        if not 0 <= int(step) < tokens.shape[1]:
+            raise _lib.VsError("sample_token: step must index a column of tokens")
+    val = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    idx = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    flags = (1 if eos_only else 0) | (2 if ban_eos else 0)
+    ws = None
+    if not one_block:
+        ws = torch.empty(int(_lib.load().vs_sample_token_workspace_bytes(rows, v)), dtype=torch.uint8,
+                         device=logits.device)
+    _lib.call("vs_sample_token", _ptr(logits), _ptr(cum), _ptr(forced), _ptr(tokens) if ngram else None,
+              int(tokens.stride(0)) if ngram else 0, int(step), ngram, _ptr(snap), _ptr(row_ids), _ptr(val),
+              _ptr(idx), rows, v, int(sampling_topk), float(sampling_topp), int(pad), int(eos), int(unk),
+              float(unk_penalty), float(temperature), flags, _ptr(ws), 0 if ws is None else ws.numel(), _stream())
+    return val, idx
+
+
+def sample_step(row_val, row_idx, tok_in, tok_out, sc_in, sc_out, ignore, finished, nfin, remaining,
+                fin_tok, fin_score, fin_pos, fin_len, reorder, bsz, beam, step, max_len, eos,
+                normalize, len_penalty, anc_in=None, anc_out=None):
+    """`beam_step` of a sampling search (vs_sample_step): one candidate per beam, (parent beam c, row c's draw)."""
+    anc_ld = 0 if anc_in is None else anc_in.shape[1]
+    _lib.call("vs_sample_step", _ptr(row_val), _ptr(row_idx), _ptr(tok_in), _ptr(tok_out), _ptr(sc_in),
+              _ptr(sc_out), _ptr(ignore), _ptr(finished), _ptr(nfin), _ptr(remaining), _ptr(fin_tok),
+              _ptr(fin_score), _ptr(fin_pos), _ptr(fin_len), _ptr(reorder), _ptr(anc_in), _ptr(anc_out),
+              int(anc_ld), int(bsz), int(beam), int(step), int(max_len), int(eos), int(bool(normalize)),
+              float(len_penalty), _stream())
 
 
 def xent_ignore(logits, labels, ignore_index):

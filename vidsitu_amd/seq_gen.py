@@ -18,7 +18,15 @@ best first).  Differences, all deliberate:
   hypothesis can finish and its own `assert step < max_len` fires;
 * `beam_size` > 16 is refused: a step asks the scoring kernel for 2*beam entries per row and its lists hold 32;
 * a single model (the reference never passes more than one), no `match_source_len`, no constraints /
-  lm_model (unused by the reference's configs: they raise).
+  lm_model (unused by the reference's configs: they raise);
+* `search_strategy` may be a `Sampling` (fairseq `search.Sampling`: `--sampling`, `--sampling-topk`,
+  `--sampling-topp`; restated from its published behaviour, parity unpinned -- docs/beam_search_parity.md,
+  "Sampling"), or the kwargs `sampling` / `sampling_topk` / `sampling_topp` / `seed` build one: each row's token is
+  drawn on the device (`vs_sample_token`) from the generator of csrc/dropout_rng.h, candidate c of a sentence is
+  (parent beam c, row c's draw), and the bookkeeping from `finalize_hypos` on is the beam search's
+  (`vs_sample_step`).  Setting both knobs is refused (fairseq silently prefers top-p).  The draws' [seed, step] state
+  lives with the decoder, so the `SeqGenCustom` of every batch continues one stream; `reseed` restarts it.  Any
+  other strategy object raises.
 """
 import math
 
@@ -67,6 +75,36 @@ class EnsembleModel(nn.Module):
         return out[0][:, -1, :]
 
 
+class Sampling:
+    """fairseq `search.Sampling` by its attribute names: the knobs of a sampling search.  -1 / -1.0 switch a knob
+    off; with both off every token of positive probability can be drawn."""
+
+    def __init__(self, tgt_dict=None, sampling_topk=-1, sampling_topp=-1.0):
+        self.tgt_dict = tgt_dict
+        self.sampling_topk, self.sampling_topp = int(sampling_topk), float(sampling_topp)
+        if self.sampling_topk != -1 and self.sampling_topk < 1:
+            raise ValueError("sampling_topk must be -1 (off) or >= 1")
+        if self.sampling_topp != -1.0 and not 0.0 < self.sampling_topp <= 1.0:
+            raise ValueError("sampling_topp must be -1.0 (off) or lie in (0, 1]")
+        if self.sampling_topk > 0 and self.sampling_topp > 0:
+            raise ValueError("sampling_topk and sampling_topp exclude each other (fairseq silently prefers top-p)")
+
+
+class _SampleStream:
+    """The [seed, step] state of a decoder's sampling searches (device int64 [2], vs_dropout_tick advances it once
+    per search step -- inside the step's graph when steps are captured, so replays draw anew)."""
+
+    def __init__(self, seed, dev):
+        self.seed = int(seed)
+        self.state = torch.tensor([self.seed, 0], dtype=torch.long, device=dev)
+
+    def reseed(self, seed):
+        """In place (step graphs hold the state's address), and never while a stream is capturing: the session
+        resolves the stream before its step loop."""
+        self.seed = int(seed)
+        self.state.copy_(torch.tensor([self.seed, 0], dtype=torch.long))
+
+
 class _DeviceSearchSession:
     """Static buffers of one generation shape (batch, beam, lengths, vocabulary rules) and, when the
     decoder keeps a KV cache, one hipGraph per step: every kernel argument of a step (position,
@@ -78,7 +116,7 @@ class _DeviceSearchSession:
     def __init__(self, key, dev):
         (self.bsz, self.beam, self.max_len, self.min_len, self.plen, self.V, self.pad, self.eos, self.unk,
          self.unk_penalty, self.temperature, self.normalize, self.len_penalty, self.kv, self.ngram,
-         _) = key
+         self.strategy, _) = key  # strategy: None (beam search) or (sampling_topk, sampling_topp)
         bsz, beam, max_len = self.bsz, self.beam, self.max_len
         rows, Lt, Ls = bsz * beam, max_len + 2, max_len + 1
         self.rows, self.Lt, self.Ls = rows, Lt, Ls
@@ -98,6 +136,7 @@ class _DeviceSearchSession:
         self.reorder = torch.empty(rows, dtype=i64, device=dev)
         self.prefix = torch.empty((bsz, self.plen), dtype=i64, device=dev) if self.plen else None
         self.k = min(2 * beam, beam * self.V - 1, self.V - 1)
+        self.snap = torch.empty(2, dtype=i64, device=dev) if self.strategy is not None else None
         self.state = None
         if self.kv:
             self.state = KVCacheState()
@@ -138,12 +177,23 @@ class _DeviceSearchSession:
         elif step < self.min_len:
             ban_eos = True
         cum = None if step == 0 else self.sc[cur][:, step - 1].contiguous()
+        anc_in, anc_out = (self.anc[cur], self.anc[1 - cur]) if self.anc is not None else (None, None)
+        if self.strategy is not None:
+            ops.dropout_tick(self.draw_state, out=self.snap)
+            row_val, row_idx = ops.sample_token(logits, cum, forced, self.snap, self.pad, self.eos, self.unk,
+                                                self.strategy[0], self.strategy[1], self.unk_penalty,
+                                                self.temperature, eos_only=step >= self.max_len, ban_eos=ban_eos,
+                                                tokens=self.tok[cur], step=step, no_repeat_ngram_size=self.ngram)
+            ops.sample_step(row_val, row_idx, self.tok[cur], self.tok[1 - cur], self.sc[cur], self.sc[1 - cur],
+                            self.ignore, self.finished, self.nfin, self.remaining, self.fin_tok, self.fin_score,
+                            self.fin_pos, self.fin_len, self.reorder, self.bsz, self.beam, step, self.max_len,
+                            self.eos, self.normalize, self.len_penalty, anc_in=anc_in, anc_out=anc_out)
+            return
         row_val, row_idx = ops.beam_topk(logits, cum, forced, self.k, self.pad, self.eos, self.unk,
                                          self.unk_penalty, self.temperature,
                                          eos_only=step >= self.max_len, ban_eos=ban_eos,
                                          tokens=self.tok[cur], step=step,
                                          no_repeat_ngram_size=self.ngram)
-        anc_in, anc_out = (self.anc[cur], self.anc[1 - cur]) if self.anc is not None else (None, None)
         ops.beam_step(row_val, row_idx, self.tok[cur], self.tok[1 - cur], self.sc[cur], self.sc[1 - cur],
                       self.ignore, self.finished, self.nfin, self.remaining, self.fin_tok, self.fin_score,
                       self.fin_pos, self.fin_len, self.reorder, self.bsz, self.beam, self.k, self.V, step,
@@ -160,6 +210,10 @@ class _DeviceSearchSession:
         graphs = self.use_graphs and self.uses >= 1 and (not encoder_outs or
                                                          getattr(dec, "uses_encoder_out", True) is False)
         self.enc = encoder_outs
+        # the draws' state is resolved here, before any step: this is where a generator that names another seed
+        # restarts the stream (a host-to-device copy, not allowed under capture, and a replayed step runs no Python).
+        # One stream per decoder and device, never replaced, so the address the step graphs hold stays the state's
+        self.draw_state = gen.sample_stream(self.tok[0].device).state if self.strategy is not None else None
         self._reset(prefix_tokens, bos_token)
         if self.state is not None and hasattr(dec, "begin_incremental"):
             # per-generation constants (encoder attention) into the state's static buffers, eagerly
@@ -203,7 +257,7 @@ class SeqGenCustom(nn.Module):
                  normalize_scores=True, len_penalty=1.0, unk_penalty=0.0, temperature=1.0,
                  match_source_len=False, no_repeat_ngram_size=0, search_strategy=None, eos=None,
                  symbols_to_strip_from_output=None, lm_model=None, lm_weight=1.0, use_kv_cache=True,
-                 device_search=True):
+                 device_search=True, sampling=False, sampling_topk=-1, sampling_topp=-1.0, seed=1):
         super().__init__()
         self.model = models if isinstance(models, EnsembleModel) else EnsembleModel(models)
         self.tgt_dict = tgt_dict
@@ -215,8 +269,16 @@ class SeqGenCustom(nn.Module):
         self.normalize_scores, self.len_penalty = normalize_scores, len_penalty
         self.unk_penalty, self.temperature = unk_penalty, temperature
         assert temperature > 0, "--temperature must be greater than 0"
-        if match_source_len or search_strategy is not None or lm_model is not None:
+        if match_source_len or lm_model is not None:
             raise NotImplementedError("option unused by the reference's configs (configs/vsitu_cfg.yml:76-85)")
+        if search_strategy is not None and not isinstance(search_strategy, Sampling):
+            raise NotImplementedError("search_strategy: only None (beam search) and Sampling are implemented")
+        if search_strategy is None and sampling:
+            search_strategy = Sampling(tgt_dict, sampling_topk, sampling_topp)
+        elif search_strategy is None and (sampling_topk != -1 or sampling_topp != -1.0):
+            raise ValueError("sampling_topk / sampling_topp need sampling=True")
+        self.search = search_strategy  # None: beam search
+        self.seed = int(seed)
         if no_repeat_ngram_size < 0 or no_repeat_ngram_size == 1:
             raise NotImplementedError(
                 "no_repeat_ngram_size must be 0 or >= 2: with 1 the reference bans every token of the row, "
@@ -248,6 +310,28 @@ class SeqGenCustom(nn.Module):
             return self._generate_device(sample, prefix_tokens, bos_token)
         return self._generate_host(sample, prefix_tokens, bos_token)
 
+    def _strategy_key(self):
+        return None if self.search is None else (self.search.sampling_topk, self.search.sampling_topp)
+
+    def sample_stream(self, dev):
+        """The decoder's draw state on `dev` (`_SampleStream`, one per device, kept for the decoder's life): made on
+        first use with this generator's seed, continued by every later `SeqGenCustom` on the same decoder that names
+        the same seed, restarted by one that names another.  Both searches call this once per generation, before
+        their first step."""
+        streams = self.model.single_model.decoder.__dict__.setdefault("_vs_sample_streams", {})
+        st = streams.get(str(dev))
+        if st is None:
+            st = streams[str(dev)] = _SampleStream(self.seed, dev)
+        elif st.seed != self.seed:
+            st.reseed(self.seed)
+        return st
+
+    def reseed(self, seed):
+        """Restart the draws' streams at step 0 of `seed` (a stream not made yet starts there anyway)."""
+        self.seed = int(seed)
+        for st in self.model.single_model.decoder.__dict__.get("_vs_sample_streams", {}).values():
+            st.reseed(seed)
+
     def _generate_device(self, sample, prefix_tokens=None, bos_token=None):
         """Same search, state on the GPU: per step one decoder call, one
         vs_beam_topk, one vs_beam_step; the KV cache is never copied (ancestry table); finished
@@ -271,7 +355,8 @@ class SeqGenCustom(nn.Module):
         dec = self.model.single_model.decoder
         key = (bsz, self.beam_size, max_len, self.min_len, plen, self.vocab_size, self.pad, self.eos,
                self.unk, float(self.unk_penalty), float(self.temperature), bool(self.normalize_scores),
-               float(self.len_penalty), bool(self.use_kv_cache), self.no_repeat_ngram_size, str(dev))
+               float(self.len_penalty), bool(self.use_kv_cache), self.no_repeat_ngram_size, self._strategy_key(),
+               str(dev))
         cache = dec.__dict__.setdefault("_vs_search_sessions", {})
         ses = cache.pop(key, None)
         if ses is None:
@@ -311,6 +396,9 @@ class SeqGenCustom(nn.Module):
             state.max_len = max_len + 2
         reorder_state = None
         batch_idxs = None
+        if self.search is not None:  # a row draws with the word of its index in the original [bsz * beam] layout
+            row_ids = torch.arange(bsz * beam, dtype=torch.long, device=dev)
+            stream = self.sample_stream(dev)
 
         for step in range(max_len + 1):  # one extra step for the EOS marker
             if reorder_state is not None:
@@ -332,24 +420,18 @@ class SeqGenCustom(nn.Module):
             elif step < self.min_len:
                 ban_eos = True  # minimum length constraint (does not apply with prefix tokens)
             cum = None if step == 0 else scores[:, step - 1].contiguous()
-            row_val, row_idx = ops.beam_topk(logits, cum, forced, k, self.pad, self.eos, self.unk,
-                                             self.unk_penalty, self.temperature,
-                                             eos_only=step >= max_len, ban_eos=ban_eos, tokens=tokens,
-                                             step=step, no_repeat_ngram_size=self.no_repeat_ngram_size)
-            # fairseq BeamSearch.step on the per-row lists: step 0 uses the first beam only
-            rv, ri = row_val.view(bsz, beam, k), row_idx.view(bsz, beam, k)
-            if step == 0:
-                cand_scores, cand_indices = rv[:, 0, :], ri[:, 0, :]
-                cand_beams = torch.zeros_like(cand_indices)
+            if self.search is not None:
+                # Sampling.step: one draw per row, candidate c = (beam c, its draw); no merge, step 0 included
+                val, idx = ops.sample_token(logits, cum, forced, ops.dropout_tick(stream.state), self.pad, self.eos,
+                                            self.unk, self.search.sampling_topk, self.search.sampling_topp,
+                                            self.unk_penalty, self.temperature, eos_only=step >= max_len,
+                                            ban_eos=ban_eos, tokens=tokens, step=step,
+                                            no_repeat_ngram_size=self.no_repeat_ngram_size, row_ids=row_ids)
+                cand_scores, cand_indices = val.view(bsz, beam), idx.view(bsz, beam)
+                cand_beams = torch.arange(beam, device=dev).unsqueeze(0).repeat(bsz, 1)
             else:
-                # the reference's count: min(2*beam, beam*V - 1) of the flattened scores; more than the
-                # k = V - 1 of a row's list where V <= 2*beam (tiny vocabularies)
-                ncand = min(cand_size, beam * V - 1)
-                flat_v = rv.reshape(bsz, beam * k)
-                order = torch.sort(flat_v, dim=1, descending=True, stable=True)[1][:, :ncand]
-                cand_scores = flat_v.gather(1, order)
-                cand_indices = ri.reshape(bsz, beam * k).gather(1, order)
-                cand_beams = order // k
+                cand_scores, cand_indices, cand_beams = self._beam_candidates(
+                    logits, cum, forced, k, ban_eos, tokens, step, max_len, bsz, cand_size)
             cand_bbsz_idx = cand_beams + bbsz_offsets
 
             eos_mask = cand_indices.eq(self.eos) & cand_scores.ne(-math.inf)
@@ -382,6 +464,8 @@ class SeqGenCustom(nn.Module):
                 cands_to_ignore = cands_to_ignore[batch_idxs]
                 scores = scores.view(bsz, -1)[batch_idxs].view(new_bsz * beam, -1)
                 tokens = tokens.view(bsz, -1)[batch_idxs].view(new_bsz * beam, -1)
+                if self.search is not None:
+                    row_ids = row_ids.view(bsz, beam)[batch_idxs].reshape(-1).contiguous()
                 bsz = new_bsz
             else:
                 batch_idxs = None
@@ -406,6 +490,23 @@ class SeqGenCustom(nn.Module):
             order = torch.sort(sc, descending=True, stable=True)[1]
             finalized[sent] = [finalized[sent][int(i)] for i in order]
         return finalized
+
+    def _beam_candidates(self, logits, cum, forced, k, ban_eos, tokens, step, max_len, bsz, cand_size):
+        """The rows' top-k lists and fairseq BeamSearch.step on them: (scores, tokens, parent beams) [bsz, ncand]."""
+        beam, V = self.beam_size, self.vocab_size
+        row_val, row_idx = ops.beam_topk(logits, cum, forced, k, self.pad, self.eos, self.unk,
+                                         self.unk_penalty, self.temperature,
+                                         eos_only=step >= max_len, ban_eos=ban_eos, tokens=tokens,
+                                         step=step, no_repeat_ngram_size=self.no_repeat_ngram_size)
+        rv, ri = row_val.view(bsz, beam, k), row_idx.view(bsz, beam, k)
+        if step == 0:  # the first beam only
+            return rv[:, 0, :], ri[:, 0, :], torch.zeros_like(ri[:, 0, :])
+        # the reference's count: min(2*beam, beam*V - 1) of the flattened scores; more than the
+        # k = V - 1 of a row's list where V <= 2*beam (tiny vocabularies)
+        ncand = min(cand_size, beam * V - 1)
+        flat_v = rv.reshape(bsz, beam * k)
+        order = torch.sort(flat_v, dim=1, descending=True, stable=True)[1][:, :ncand]
+        return flat_v.gather(1, order), ri.reshape(bsz, beam * k).gather(1, order), order // k
 
     def finalize_hypos(self, step, bbsz_idx, eos_scores, tokens, scores, finalized, finished,
                        beam_size, max_len):

@@ -612,6 +612,19 @@ int vs_gemm_bf16_ld_ws(const float* a, const float* b, const float* bias, const 
 int vs_pack_rows_f32(const float* src, float* dst, int R, int K, void* stream);
 int vs_gemm_nt_f32_packed(const float* x_packed, const float* w_packed, const float* b, const float* res,
                           float* y, int M, int N, int K, int act, int y_packed, void* stream);
+/* The same GEMM with bf16 weights: y = act(bf16(x) . bf16(w)^T + b) + res, fp32 accumulators, 1 <= M <= 64,
+ * K % 128 == 0; act, b, res and y_packed as vs_gemm_nt_f32_packed.  vs_pack_rows_bf16 writes the weight image:
+ * src[R][K] (K % 32 == 0) rounded to bf16 (nearest, ties to even) in 1-KB blocks of 16 rows x 32 k values in
+ * v_mfma_f32_16x16x32_bf16 operand order (block (r/16, k/32) at index (r/16)*(K/32) + k/32; lane (k%32/8)*16 + r%16
+ * holds the eight values k%8 = 0..7; rows up to the next multiple of 16 are zero): dst holds ceil16(R) * K values.
+ * x_packed stays the fp32 image of vs_pack_rows_f32; the kernel rounds it as it loads.  _plan is host-only: the index
+ * (0 .. _plan_count() - 1) of the tile shape the launch takes for these sizes, -1 where the entry point refuses
+ * them -- one decision function behind both. */
+int vs_pack_rows_bf16(const float* src, uint16_t* dst, int R, int K, void* stream);
+int vs_gemm_nt_bf16_packed(const float* x_packed, const uint16_t* w_packed, const float* b, const float* res,
+                           float* y, int M, int N, int K, int act, int y_packed, void* stream);
+int vs_gemm_nt_bf16_packed_plan(int M, int N, int K);
+int vs_gemm_nt_bf16_packed_plan_count(void);
 /* LayerNorm(x) * gamma + beta written fragment-major (D % 16 == 0, D <= 2048). */
 int vs_layernorm_fwd_packed(const float* x, const float* gamma, const float* beta, float* y_packed,
                             int rows, int D, float eps, void* stream);

@@ -45,6 +45,7 @@ import torch.distributed as dist
 
 from vidsitu_amd import checkpoint, dist_launch, lr_sched, synth_data
 from vidsitu_amd.extended_config import get_cfg
+from vidsitu_amd.hf_gpt2_fseq import GPT2LMHeadModelHip
 from vidsitu_amd.mdl_selector import get_mdl_loss_eval
 from vidsitu_amd.optim import ArenaAdam, ParamArena
 from vidsitu_amd.train_step import TrainStep
@@ -99,6 +100,10 @@ def main_fn(rank, cfg, steps, graph=True, val_every=0):
     sel = get_mdl_loss_eval(cfg)
     torch.manual_seed(0)
     mdl = sel["mdl"](cfg=cfg, comm=comm).to(dev)
+    if rank == 0:
+        for m in mdl.modules():
+            if isinstance(m, GPT2LMHeadModelHip):  # the two opt-in precision switches, as the model holds them
+                print(f"[{cfg.uid}] GPT-2 decoder: matmul {m.matmul}, decode_matmul {m.decode_matmul}")
     loss_fn = sel["loss"](cfg, comm)
     eval_fn = sel["evl"](cfg, comm, dev)
     arena = ParamArena(mdl)

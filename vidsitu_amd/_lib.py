@@ -191,6 +191,10 @@ SIGNATURES = {
     "vs_ingest_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _i, _i, _p, _p, _i,
                           _p]),
     "vs_gemm_nt_f32_packed": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "vs_pack_rows_bf16": (_i, [_p, _p, _i, _i, _p]),
+    "vs_gemm_nt_bf16_packed": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "vs_gemm_nt_bf16_packed_plan": (_i, [_i, _i, _i]),
+    "vs_gemm_nt_bf16_packed_plan_count": (_i, []),
     "vs_layernorm_fwd_packed": (_i, [_p, _p, _p, _p, _i, _i, _f, _p]),
     "vs_beam_topk_workspace_bytes": (_sz, [_i, _i, _i]),
     "vs_kv_gather": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),

@@ -548,6 +548,225 @@ extern "C" int vs_gemm_nt_f32_packed(const float* x_packed, const float* w_packe
   return VS_OK;
 }
 
+// ---- the same decode-step GEMM with bf16 weights (GPT-2's opt-in decode_matmul = "bf16") -------------------------
+// w: the fragment-major bf16 image of vs_pack_rows_bf16 (a 16-row x 32-k block = 1 KB in v_mfma_f32_16x16x32_bf16
+// operand order: lane l holds row l & 15, k = 8 (l >> 4) + 0..7, one 16-byte load).  x: still the fp32 image of
+// vs_pack_rows_f32 -- no producer changes; for a 32-wide k chunk c, lane (kq = l >> 4, row = l & 15) takes the two
+// float4s of fp32 block 2c + (kq >> 1) at in-block lanes (2 (kq & 1)) * 16 + row and (2 (kq & 1) + 1) * 16 + row
+// (64 floats apart) and rounds them to bf16, nearest-even, when the stage is consumed.  Structure of
+// linear_skinny_kernel: NW waves split K, two register stages fenced by scheduling barriers, unconditional loads, the
+// NW partial tiles added through LDS in wave order, the XCD-neighbour block mapping, the same epilogue (the C/D layout
+// of 16x16x32_bf16 is that of 16x16x4_f32).  One difference: inside a group of NW * CH chunks wave w owns the CH
+// consecutive chunks w * CH.., and counts its own groups -- K % 128 == 0 with CH <= 2 makes a wave's chunks of the
+// last, partial group all present or all absent, so every tile shape takes every K % 128 == 0 (waves past K idle)
+// and the choice of a tile shape depends on M and N alone (bf16pk_plan).
+template <int RB, int CB, int CH>
+struct LskStage16 {
+  float4 a[RB][CH][2];
+  uint4 bw[CB][CH];
+};
+
+__device__ __forceinline__ bf16x8 lsk_round8(const float4& lo, const float4& hi) {
+  bf16x8 v;
+  v[0] = (__bf16)lo.x; v[1] = (__bf16)lo.y; v[2] = (__bf16)lo.z; v[3] = (__bf16)lo.w;
+  v[4] = (__bf16)hi.x; v[5] = (__bf16)hi.y; v[6] = (__bf16)hi.z; v[7] = (__bf16)hi.w;
+  return v;
+}
+
+template <int RB, int CB, int CH, int NW>
+__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void linear_skinny_bf16_kernel(
+    const float* __restrict__ x, const uint16_t* __restrict__ w, const float* __restrict__ b,
+    const float* res, float* y, int M, int N, int K, int act, int tiles, int rgroups, int ypk) {
+  static_assert(CH == 1 || CH == 2, "a wave's chunks of a partial group must be all present or all absent");
+  extern __shared__ lsk_v4f lsk_red16[];  // [NW waves][RB*CB tiles][64 lanes]
+  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  const int tile = (slot / rgroups) * 8 + xcd, rg = slot % rgroups;
+  if (tile >= tiles) return;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n0 = tile * (16 * CB), m0 = rg * (16 * RB), col = lane & 15, kq = lane >> 4;
+  const int kc32 = K >> 5;  // 32-wide chunks of K; 512 bf16 of w and 512 floats of x per chunk and 16-row block
+  const uint16_t* wp[CB];
+#pragma unroll
+  for (int cb = 0; cb < CB; ++cb) {
+    const int nt16 = (N + 15) >> 4;
+    const int t16 = n0 / 16 + cb < nt16 ? n0 / 16 + cb : nt16 - 1;
+    wp[cb] = w + ((long long)t16 * kc32 + wave * CH) * 512 + lane * 8;
+  }
+  const float* xp[RB];
+#pragma unroll
+  for (int rb = 0; rb < RB; ++rb)
+    xp[rb] = x + ((long long)(m0 / 16 + rb) * kc32 + wave * CH) * 512 + (kq >> 1) * 256 + ((kq & 1) * 32 + col) * 4;
+  lsk_v4f acc[RB][CB];
+#pragma unroll
+  for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) acc[rb][cb] = lsk_v4f{0.f, 0.f, 0.f, 0.f};
+
+  // groups of this wave: those g with chunk g * NW * CH + wave * CH inside K
+  const int groups = (kc32 - wave * CH + NW * CH - 1) / (NW * CH);
+  auto load = [&](LskStage16<RB, CB, CH>& st, int g) {
+    const int off = g * (NW * CH * 512);
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+#pragma unroll
+      for (int cb = 0; cb < CB; ++cb) st.bw[cb][c] = *(const uint4*)(wp[cb] + off + c * 512);
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb) {
+        st.a[rb][c][0] = *(const float4*)(xp[rb] + off + c * 512);
+        st.a[rb][c][1] = *(const float4*)(xp[rb] + off + c * 512 + 64);
+      }
+    }
+  };
+  auto compute = [&](const LskStage16<RB, CB, CH>& st) {
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      bf16x8 af[RB];
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb) af[rb] = lsk_round8(st.a[rb][c][0], st.a[rb][c][1]);
+#pragma unroll
+      for (int cb = 0; cb < CB; ++cb) {
+        const bf16x8 bf = __builtin_bit_cast(bf16x8, st.bw[cb][c]);
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb)
+          acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[rb], bf, acc[rb][cb], 0, 0, 0);
+      }
+    }
+  };
+  if (groups > 0) {  // (wave-uniform: a wave whose first chunk lies past K loads nothing and adds zeros)
+    LskStage16<RB, CB, CH> s0, s1;
+    load(s0, 0);
+    const int glast = groups - 1;
+    int g = 0;
+    for (; g + 2 <= groups; g += 2) {
+      load(s1, g + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      compute(s0);
+      __builtin_amdgcn_sched_barrier(0);
+      if (g + 2 < groups) load(s0, g + 2 < glast ? g + 2 : glast);  // (uniform; skipped on the last trip)
+      __builtin_amdgcn_sched_barrier(0);
+      compute(s1);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (g < groups) compute(s0);  // odd tail: the loop's last load (or the prologue's) fetched it
+  }
+  constexpr int NT = RB * CB;
+#pragma unroll
+  for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) lsk_red16[(wave * NT + rb * CB + cb) * 64 + lane] = acc[rb][cb];
+  __syncthreads();
+  // the epilogue of linear_skinny_kernel, statement for statement
+  for (int t = wave; t < NT; t += NW) {
+    const int rb = t / CB, cb = t % CB;
+    lsk_v4f v = lsk_red16[t * 64 + lane];
+#pragma unroll
+    for (int q = 1; q < NW; ++q) v += lsk_red16[(q * NT + t) * 64 + lane];
+    const int n = n0 + cb * 16 + col;
+    if (n >= N) continue;
+    const float bias = b ? b[n] : 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int m = m0 + rb * 16 + 4 * kq + e;
+      if (m < M) {
+        float sv = v[e] + bias;
+        if (act == 1) sv = fmaxf(sv, 0.f);
+        else if (act == 2) sv = gelu_new_f(sv);
+        if (res) sv += res[(long long)m * N + n];
+        if (ypk) y[(((long long)(m >> 4) * (N >> 4) + (n >> 4)) * 64 + ((n & 15) >> 2) * 16 + (m & 15)) * 4 + (n & 3)] = sv;
+        else y[(long long)m * N + n] = sv;
+      }
+    }
+  }
+}
+
+template <int RB, int CB, int CH, int NW>
+static void launch_skinny16_cfg(const float* x, const uint16_t* w, const float* b, const float* res, float* y,
+                                int M, int N, int K, int act, int ypk, hipStream_t st) {
+  constexpr int smem = NW * RB * CB * 64 * 16;
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)linear_skinny_bf16_kernel<RB, CB, CH, NW>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    attr = true;
+  }
+  const int tiles = (N + 16 * CB - 1) / (16 * CB), tiles8 = (tiles + 7) & ~7;
+  const int rgroups = (M + 16 * RB - 1) / (16 * RB);
+  hipLaunchKernelGGL((linear_skinny_bf16_kernel<RB, CB, CH, NW>), dim3(tiles8 * rgroups), dim3(64 * NW), smem, st,
+                     x, w, b, res, y, M, N, K, act, tiles, rgroups, ypk);
+}
+
+// The one decision behind vs_gemm_nt_bf16_packed and vs_gemm_nt_bf16_packed_plan: the index of the tile shape, -1 where
+// the entry point refuses.  The largest tile that still yields ~190 blocks (rbn = 16-row blocks of M):
+//   0..3  <rbn,4,1, 4>  all rows x 64 columns, K in 4 waves x 32    N >= 190 * 64 (the lm_head)
+//   4..7  <rbn,1,2, 8>  all rows x 16 columns, K in 8 waves x 64    N >= 190 * 16 (c_attn, mlp.c_fc)
+//   8     <1,  1,2,16>  16 rows x 16 columns,  K in 16 waves x 64   the rest; a column tile's row groups are neighbours
+//                                                                   on one XCD (attn.c_proj, mlp.c_proj)
+enum { BF16PK_PLANS = 9 };
+static int bf16pk_plan(int M, int N, int K) {
+  if (M < 1 || M > 64 || N < 1 || K < 1 || (K & 127) != 0) return -1;
+  const int rbn = (M + 15) / 16;
+  if (N >= 190 * 64) return rbn - 1;
+  if (N >= 190 * 16) return 4 + rbn - 1;
+  return 8;
+}
+
+// Fragment-major bf16 image of a row-major fp32 matrix src[R][K] (K % 32 == 0): block (r / 16, k / 32) of 16 rows x 32
+// k values is 1 KB at index (r / 16) * (K / 32) + k / 32; inside, lane (k % 32 / 8) * 16 + r % 16 holds the eight
+// values k % 8 = 0..7, rounded to nearest-even -- the v_mfma_f32_16x16x32_bf16 operand order.  Rows up to the next
+// multiple of 16 are zero-filled.
+__global__ void pack_rows_bf16_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst, int R, int K) {
+  const long long blk = blockIdx.x;  // one 1-KB block per wave; 4 per workgroup
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int kc32 = K >> 5;
+  const long long id = blk * 4 + wave;
+  const long long nblk = (long long)((R + 15) >> 4) * kc32;
+  if (id >= nblk) return;
+  const int rblk = (int)(id / kc32), kc = (int)(id % kc32);
+  const int r = rblk * 16 + (lane & 15), k = kc * 32 + (lane >> 4) * 8;
+  float f[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (r < R) {
+    *(float4*)f = *(const float4*)(src + (long long)r * K + k);
+    *(float4*)(f + 4) = *(const float4*)(src + (long long)r * K + k + 4);
+  }
+  *(uint4*)(dst + id * 512 + lane * 8) = pack8_bf16(f);
+}
+
+extern "C" int vs_pack_rows_bf16(const float* src, uint16_t* dst, int R, int K, void* stream) {
+  VS_CHECK_ARG(src && dst && R > 0 && K > 0 && (K & 31) == 0, "K must be a multiple of 32");
+  VS_CHECK_ARG((((uintptr_t)src | (uintptr_t)dst) & 15) == 0, "16-byte aligned pointers");
+  const long long nblk = (long long)((R + 15) >> 4) * (K >> 5);
+  hipLaunchKernelGGL(pack_rows_bf16_kernel, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                     src, dst, R, K);
+  VS_CHECK_LAUNCH();
+  return VS_OK;
+}
+
+extern "C" int vs_gemm_nt_bf16_packed_plan(int M, int N, int K) { return bf16pk_plan(M, N, K); }
+extern "C" int vs_gemm_nt_bf16_packed_plan_count(void) { return BF16PK_PLANS; }
+
+extern "C" int vs_gemm_nt_bf16_packed(const float* x_packed, const uint16_t* w_packed, const float* b,
+                                      const float* res, float* y, int M, int N, int K, int act, int y_packed,
+                                      void* stream) {
+  VS_CHECK_ARG(x_packed && w_packed && y && M > 0 && M <= 64 && N > 0 && K > 0, "1..64 rows");
+  VS_CHECK_ARG(act >= 0 && act <= 2, "act must be 0 (none), 1 (relu) or 2 (gelu_new)");
+  VS_CHECK_ARG((K & 127) == 0, "K must be a multiple of 128");
+  VS_CHECK_ARG(!y_packed || (N & 15) == 0, "a packed output needs N % 16 == 0");
+  VS_CHECK_ARG((((uintptr_t)x_packed | (uintptr_t)w_packed) & 15) == 0, "unaligned operands");
+  hipStream_t st = (hipStream_t)stream;
+  switch (bf16pk_plan(M, N, K)) {
+#define VS_BF16PK(P, RB, CB, CH, NW) \
+  case P: launch_skinny16_cfg<RB, CB, CH, NW>(x_packed, w_packed, b, res, y, M, N, K, act, y_packed, st); break;
+    VS_BF16PK(0, 1, 4, 1, 4) VS_BF16PK(1, 2, 4, 1, 4) VS_BF16PK(2, 3, 4, 1, 4) VS_BF16PK(3, 4, 4, 1, 4)
+    VS_BF16PK(4, 1, 1, 2, 8) VS_BF16PK(5, 2, 1, 2, 8) VS_BF16PK(6, 3, 1, 2, 8) VS_BF16PK(7, 4, 1, 2, 8)
+    VS_BF16PK(8, 1, 1, 2, 16)
+#undef VS_BF16PK
+    default: VS_CHECK_ARG(false, "no tile shape for these sizes");
+  }
+  VS_CHECK_LAUNCH();
+  return VS_OK;
+}
+
 static int linear_small_m(const float* x, const float* w, const float* b, const float* res, float* y,
                           int M, int N, int K, int act, hipStream_t st) {
   const int gx = (N + 3) / 4;

@@ -160,6 +160,7 @@ class CfgProcessor:
         # and the key can be overridden on top of it
         cfg.mdl.setdefault("gpt2_dropout", 0.0)
         cfg.mdl.setdefault("gpt2_matmul", "fp32")
+        cfg.mdl.setdefault("gpt2_decode_matmul", "fp32")
         cfg.mdl.setdefault("rob_dropout", 0.0)
         cfg.mdl.setdefault("rob_matmul", "fp32")
         for k, v in (("sampling", False), ("sampling_topk", -1), ("sampling_topp", -1.0), ("seed", 1)):

@@ -29,6 +29,15 @@ loads them, no bf16 copy of a weight or activation exists).  Everything else -- 
 gelu, residuals, dropout, the loss, bias and embedding gradients, and the whole cached decode step -- is fp32 in both
 modes, so the mode changes no generated token for given weights.
 
+Generation has a switch of its own: `decode_matmul="bf16"` (default `"fp32"`, under which nothing changes bit for bit)
+rounds x and W of the five dense projections of `forward_step` to bf16, with fp32 accumulation.  Up to 64 rows (with
+d_model % 128 == 0 and a head size of 16, 32 or 64) the step is the packed one on `ops.gemm_nt_packed_bf16`: the weights
+are kept as fragment-major bf16 images (`_wpk16`, built once like `_wpk`, which this mode never builds), the
+activation images stay fp32 and are rounded by the kernel as it loads them; 1..16 rows take this path too.  Above 64
+rows, or at other dimensions, the step runs `_block` / `_head` on `ops.gemm_nt(bf16=True)`.  Embedding, layernorms,
+`attn_decode`, the KV cache, gelu and the residuals stay fp32.  The weights are rounded, so this mode MAY change
+generated tokens; `forward_logits`, `forward_train`, `backward` and the no-KV-cache path follow `matmul` alone.
+
 `GPT2LMHeadModelHip` is a `flat_module.FlatParamModule`: registration, state dict, the cached weight copies and the
 autograd node (`FlatTrainFn`) live there; this file keeps the names / shapes, the arithmetic and `KVCacheState`.
 """
@@ -45,6 +54,7 @@ GPT2_DIMS = {
     "gpt2": (12, 768, 12, 1024, 50257),
     "gpt2-medium": (24, 1024, 16, 1024, 50257),
     "gpt2-synth-tiny": (2, 64, 4, 64, 97),  # tests / smoke only
+    "gpt2-synth-d128": (2, 128, 4, 64, 97),  # tests only: the smallest model whose decode step takes the packed GEMMs
 }
 
 
@@ -80,18 +90,23 @@ class KVCacheState:
 
 class GPT2LMHeadModelHip(FlatParamModule):
     _CACHES = ("_wt",   # K-contiguous ([out][in]) copies of the Conv1D weights for the kernels
-               "_wpk")  # fragment-major copies for the decode-step GEMMs (ops.gemm_nt_packed)
+               "_wpk",  # fragment-major copies for the decode-step GEMMs (ops.gemm_nt_packed)
+               "_wpk16")  # their bf16 images (ops.gemm_nt_packed_bf16), built instead of `_wpk` by decode_matmul="bf16"
     _CAPTURE_MSG = "GPT-2 weight copies must exist before a graph capture (run one eager step first)"
 
     _DROP_CAPTURE_MSG = "the GPT-2 dropout state must exist before a graph capture (run one eager step first)"
 
     def __init__(self, n_layer, d_model, n_head, n_positions, vocab_size, embd_pdrop=0.0, attn_pdrop=0.0,
-                 resid_pdrop=0.0, matmul="fp32"):
+                 resid_pdrop=0.0, matmul="fp32", decode_matmul="fp32"):
         super().__init__()
         if matmul not in ("fp32", "bf16"):
             raise ValueError(f'matmul must be "fp32" or "bf16", got {matmul!r}')
+        if decode_matmul not in ("fp32", "bf16"):
+            raise ValueError(f'decode_matmul must be "fp32" or "bf16", got {decode_matmul!r}')
         self.matmul = matmul
         self._bf16 = matmul == "bf16"  # operand precision of the whole-sequence GEMMs (module docstring)
+        self.decode_matmul = decode_matmul
+        self._bf16_step = decode_matmul == "bf16"  # operand precision of the cached decode step's GEMMs
         self.n_layer, self.d_model, self.n_head, self.n_positions = n_layer, d_model, n_head, n_positions
         self.embd_pdrop, self.attn_pdrop, self.resid_pdrop = float(embd_pdrop), float(attn_pdrop), float(resid_pdrop)
         # (thr, scale) per probability, None at p = 0 (that site then runs today's launches); refuses p outside [0, 1)
@@ -145,13 +160,19 @@ class GPT2LMHeadModelHip(FlatParamModule):
         new[:n] = old.detach()[:n]
         setattr(self, "transformer__wte__weight", nn.Parameter(new))
         self.config.vocab_size = new_size
-        self._drop_copies()  # `_wpk` may hold a packed copy of the old table
+        self._drop_copies()  # `_wpk` / `_wpk16` may hold a packed copy of the old table
 
     def _wp(self, name, transposed=True):
         """Fragment-major copy of a weight ([out][in] orientation) for the 17..64-row decode GEMMs."""
         w = self.P(name)
         return self._copy(self._wpk, name, w,
                           lambda: ops.pack_rows_f32(self._w(name) if transposed else w.detach()))
+
+    def _wp16(self, name, transposed=True):
+        """Fragment-major bf16 image of a weight ([out][in] orientation) for the bf16-mode decode GEMMs."""
+        w = self.P(name)
+        return self._copy(self._wpk16, name, w,
+                          lambda: ops.pack_rows_bf16(w.detach().t() if transposed else w.detach()))
 
     def _w(self, name):
         """[out][in] view of a Conv1D weight (transposed once, after load / device move)."""
@@ -208,36 +229,38 @@ class GPT2LMHeadModelHip(FlatParamModule):
         t = state.len
         h = ops.gpt2_embed(last_tokens.view(rows, 1), self.P("transformer.wte.weight"),
                            self.P("transformer.wpe.weight"), pos0=t)
-        if 16 < rows <= 64 and self.d_model % 128 == 0 and (self.d_model // self.n_head) in (16, 32, 64):
+        # the packed step: 17..64 rows in fp32 mode (up to 16 rows one wave streams one weight row), 1..64 in bf16 mode
+        if ((16 < rows or self._bf16_step) and rows <= 64 and self.d_model % 128 == 0
+                and (self.d_model // self.n_head) in (16, 32, 64)):
             return self._forward_step_packed(h, rows, state, key_mask, t)
         for i in range(self.n_layer):
             h = self._block(i, h, lambda li, qkv: ops.attn_decode(qkv, state.k[li][:rows], state.v[li][:rows],
-                                                                  key_mask, t, ancestry=state.anc))
+                                                                  key_mask, t, ancestry=state.anc),
+                            bf16=self._bf16_step)
         state.len = t + 1
-        return self._head(h)
+        return self._head(h, bf16=self._bf16_step)
 
     def _forward_step_packed(self, h, rows, state, key_mask, t):
         """The cached step for 17..64 rows (sentences x beams): every GEMM operand fragment-major --
         weights packed once, activations written in that layout by their producers (layernorm,
-        attention, the gelu epilogue) -- so each MFMA fragment load is one contiguous KB."""
+        attention, the gelu epilogue) -- so each MFMA fragment load is one contiguous KB.  In bf16 mode
+        (1..64 rows) the weights are bf16 images and the kernel rounds the fp32 activation images as it loads them."""
         d, v = self.d_model, self.P("transformer.wte.weight").shape[0]
+        gemm, wp = (ops.gemm_nt_packed_bf16, self._wp16) if self._bf16_step else (ops.gemm_nt_packed, self._wp)
         for i in range(self.n_layer):
             q = f"transformer.h.{i}."
             a = ops.layernorm_fwd_packed(h, self.P(q + "ln_1.weight"), self.P(q + "ln_1.bias"), 1e-5)
-            qkv = ops.gemm_nt_packed(a, self._wp(q + "attn.c_attn.weight"), rows, 3 * d, d,
-                                     b=self.P(q + "attn.c_attn.bias"))
+            qkv = gemm(a, wp(q + "attn.c_attn.weight"), rows, 3 * d, d, b=self.P(q + "attn.c_attn.bias"))
             o = ops.attn_decode(qkv, state.k[i][:rows], state.v[i][:rows], key_mask, t, ancestry=state.anc,
                                 out_packed=True)
-            h = ops.gemm_nt_packed(o, self._wp(q + "attn.c_proj.weight"), rows, d, d,
-                                   b=self.P(q + "attn.c_proj.bias"), res=h)
+            h = gemm(o, wp(q + "attn.c_proj.weight"), rows, d, d, b=self.P(q + "attn.c_proj.bias"), res=h)
             m = ops.layernorm_fwd_packed(h, self.P(q + "ln_2.weight"), self.P(q + "ln_2.bias"), 1e-5)
-            f = ops.gemm_nt_packed(m, self._wp(q + "mlp.c_fc.weight"), rows, 4 * d, d,
-                                   b=self.P(q + "mlp.c_fc.bias"), act=ops.ACT_GELU_NEW, y_packed=True)
-            h = ops.gemm_nt_packed(f, self._wp(q + "mlp.c_proj.weight"), rows, d, 4 * d,
-                                   b=self.P(q + "mlp.c_proj.bias"), res=h)
+            f = gemm(m, wp(q + "mlp.c_fc.weight"), rows, 4 * d, d, b=self.P(q + "mlp.c_fc.bias"),
+                     act=ops.ACT_GELU_NEW, y_packed=True)
+            h = gemm(f, wp(q + "mlp.c_proj.weight"), rows, d, 4 * d, b=self.P(q + "mlp.c_proj.bias"), res=h)
         state.len = t + 1
         hf = ops.layernorm_fwd_packed(h, self.P("transformer.ln_f.weight"), self.P("transformer.ln_f.bias"), 1e-5)
-        return ops.gemm_nt_packed(hf, self._wp("transformer.wte.weight", transposed=False), rows, v, d)
+        return gemm(hf, wp("transformer.wte.weight", transposed=False), rows, v, d)
 
     @torch.no_grad()
     def generate_greedy(self, input_ids, max_length, pad_token_id, eos_token_id, sync_every=8):
@@ -399,7 +422,8 @@ class HuggingFaceGPT2Decoder(nn.Module):
         pdrop = float(args.mdl.get("gpt2_dropout", 0.0))
         # "fp32" | "bf16": operand precision of the whole-sequence GEMMs (this project's own switch)
         self.model = GPT2LMHeadModelHip(*dims, embd_pdrop=pdrop, attn_pdrop=pdrop, resid_pdrop=pdrop,
-                                        matmul=str(args.mdl.get("gpt2_matmul", "fp32")))
+                                        matmul=str(args.mdl.get("gpt2_matmul", "fp32")),
+                                        decode_matmul=str(args.mdl.get("gpt2_decode_matmul", "fp32")))
         if state_dict is not None:
             self.model.load_state_dict(state_dict)
         self.voc_size = len(dictionary)

@@ -327,7 +327,8 @@ class Simple_GPT2(nn.Module):
     def build_model(self):
         pdrop = float(self.cfg.get("gpt2_dropout", 0.0))  # one number for huggingface's three probabilities
         self.gpt2_mdl = GPT2LMHeadModelHip(*GPT2_DIMS[self.cfg.gpt2_mdl_name], embd_pdrop=pdrop, attn_pdrop=pdrop,
-                                           resid_pdrop=pdrop, matmul=str(self.cfg.get("gpt2_matmul", "fp32")))
+                                           resid_pdrop=pdrop, matmul=str(self.cfg.get("gpt2_matmul", "fp32")),
+                                           decode_matmul=str(self.cfg.get("gpt2_decode_matmul", "fp32")))
         self.voc_size = len(self.comm.gpt2_hf_tok)
         self.gpt2_mdl.resize_token_embeddings(self.voc_size)
         self.pad_index = self.comm.gpt2_hf_tok.pad_token_id

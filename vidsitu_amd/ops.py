@@ -1344,6 +1344,40 @@ def gemm_nt_packed(x_packed, w_packed, m, n, k, b=None, res=None, act=ACT_NONE, 
     return y
 
 
+def pack_rows_bf16(src):
+    """Row-major f32 [R, K] (K % 32 == 0) -> fragment-major bf16 image (flat int16, ceil16(R) * K values, rounded to
+    nearest-even) for `gemm_nt_packed_bf16` (vs_pack_rows_bf16: 16 x 32 blocks in v_mfma_f32_16x16x32_bf16 operand
+    order)."""
+    src = _f32c(src)
+    r, k = src.shape
+    dst = torch.empty(_pad16(r) * k, dtype=torch.int16, device=src.device)
+    _lib.call("vs_pack_rows_bf16", _ptr(src), _ptr(dst), r, k, _stream())
+    return dst
+
+
+def unpack_rows_bf16(packed, r, k):
+    """Inverse of pack_rows_bf16 as torch ops (tests / debugging): the bf16 values as fp32 [r, k]."""
+    rows = packed.view(torch.bfloat16).view(_pad16(r) // 16, k // 32, 4, 16, 8).permute(0, 3, 1, 2, 4)
+    return rows.reshape(_pad16(r), k)[:r].float()
+
+
+def gemm_nt_packed_bf16(x_packed, w_packed16, m, n, k, b=None, res=None, act=ACT_NONE, y_packed=False):
+    """act(bf16(x) @ bf16(w)^T + b) + res for 1..64 rows, fp32 accumulation: x fragment-major fp32 (pack_rows_f32's
+    layout, rounded by the kernel), w the image of pack_rows_bf16; the output is row-major [m, n], or fragment-major
+    fp32 (flat, ceil16(m) * n floats) when y_packed."""
+    if x_packed.numel() < _pad16(m) * k or w_packed16.numel() < _pad16(n) * k:
+        raise _lib.VsError("gemm_nt_packed_bf16: packed operand too small for the given shape")
+    if x_packed.dtype != torch.float32 or w_packed16.element_size() != 2:
+        raise _lib.VsError("gemm_nt_packed_bf16: x must be the fp32 image, w the 16-bit image of pack_rows_bf16")
+    if y_packed:
+        y = torch.empty(_pad16(m) * n, dtype=torch.float32, device=x_packed.device)
+    else:
+        y = torch.empty((m, n), dtype=torch.float32, device=x_packed.device)
+    _lib.call("vs_gemm_nt_bf16_packed", _ptr(x_packed), _ptr(w_packed16), _ptr(b), _ptr(res), _ptr(y), int(m),
+              int(n), int(k), int(act), int(bool(y_packed)), _stream())
+    return y
+
+
 def layernorm_fwd_packed(x, gamma, beta, eps=1e-5):
     """LayerNorm of f32 [rows, D] written fragment-major (flat, ceil16(rows) * D floats)."""
     x = _f32c(x)

@@ -857,6 +857,29 @@ int vs_attn_tiled_bwd(const float* qkv, const uint8_t* key_mask, const float* do
  * (backward != 0) holds sequences of L positions at head width dh, by the launchers' own formulas; else 0. */
 int vs_attn_resident_fits(int causal, int L, int dh, int backward);
 
+/* ---- Encoder (cross) attention of the fairseq decoder, csrc/attn_cross.hip, fp32 on v_mfma_f32_16x16x4_f32.
+ * q[R*L, D] (D = H*dh), kv[R*S, 2D] (k | v), key_mask u8 [R, S] (1 = valid) or NULL, out[R*L, D]:
+ * s_ij = q_i.k_j / sqrt(dh), softmax over the S keys of the row's source, out = p.v with the heads merged.  Not causal,
+ * no dropout.  Masked keys weigh exactly 0; a row whose mask is all zero runs unmasked (vs_attn_pad_fwd's rule).
+ * K and V of a head are LDS-resident: dh is 16, 32, 64 or 128 and S is bounded by the LDS (dh = 128: S <= 112 forward,
+ * S <= 96 backward; vs_attn_cross_fits answers by the launchers' own formulas); L is free.  A shape outside returns
+ * VS_ERR_BAD_ARG with a message naming the limit and writes nothing. */
+int vs_attn_cross_fwd(const float* q, const float* kv, const uint8_t* key_mask, float* out, int R, int L, int S, int H,
+                      int dh, void* stream);
+/* Backward: dq[R*L, D] and dkv[R*S, 2D] from dout[R*L, D], p recomputed; two launches (per query tile: dq and the p /
+ * dS rows into the scratch [R*H][2][L][ceil16(S)]; per key tile: dk, dv); every element of dq and dkv is overwritten;
+ * no atomics, fixed summation order.  A short scratch is an error, nothing written. */
+size_t vs_attn_cross_bwd_scratch_bytes(int R, int L, int S, int H);
+int vs_attn_cross_bwd(const float* q, const float* kv, const uint8_t* key_mask, const float* dout, float* dq,
+                      float* dkv, void* ws, size_t ws_bytes, int R, int L, int S, int H, int dh, void* stream);
+int vs_attn_cross_fits(int L, int S, int dh, int backward);
+/* One cached decode step: q[rows, D], one query per (row, head), against the encoder caches K, V [rows, H, S, dh]
+ * (S <= 2048) written once per generation by vs_attn_cross_kv_split from kv[rows*S, 2D]; out[rows, D].  The masking
+ * rule is the forward's.  No host reads: capturable. */
+int vs_attn_cross_decode(const float* q, const float* kcache, const float* vcache, const uint8_t* key_mask, float* out,
+                         int rows, int S, int H, int dh, void* stream);
+int vs_attn_cross_kv_split(const float* kv, float* kcache, float* vcache, int R, int S, int H, int dh, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

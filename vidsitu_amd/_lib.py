@@ -232,6 +232,12 @@ SIGNATURES = {
     "vs_attn_tiled_bwd_scratch_bytes": (_sz, [_i, _i, _i]),
     "vs_attn_tiled_bwd": (_i, [_p, _p, _p, _p, _p, _sz, _i, _i, _i, _i, _i, _p, _u32, _u32, _f, _p]),
     "vs_attn_resident_fits": (_i, [_i, _i, _i, _i]),
+    "vs_attn_cross_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "vs_attn_cross_bwd_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "vs_attn_cross_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _sz, _i, _i, _i, _i, _i, _p]),
+    "vs_attn_cross_fits": (_i, [_i, _i, _i, _i]),
+    "vs_attn_cross_decode": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "vs_attn_cross_kv_split": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "vs_roberta_embed": (_i,[_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "vs_gelu_erf_fwd": (_i, [_p, _p, _i64, _p]),
     "vs_gelu_erf_bwd": (_i, [_p, _p, _p, _i64, _p]),

@@ -1,7 +1,7 @@
 // What the whole-sequence attention kernels share: the exact-fp32 matrix instruction with its LDS staging and the
 // dropout draw of the matrix-unit kernels (roberta_ops.hip, attn_tiled.hip), and the LDS budget of the resident
-// kernels (roberta_ops.hip, gpt2_ops.hip) -- each formula once, for the launchers' own checks and for
-// vs_attn_resident_fits.
+// kernels (roberta_ops.hip, gpt2_ops.hip, attn_cross.hip) -- each formula once, for the launchers' own checks and for
+// vs_attn_resident_fits / vs_attn_cross_fits.
 #pragma once
 #include "common.h"
 #include "dropout_rng.h"
@@ -65,6 +65,13 @@ static inline size_t ap_bwd_smem(int L, int dh) {
   return ((size_t)2 * Lp * (dh + 4) + 8 * 16 * (Lp + 4)) * sizeof(float);
 }
 static inline bool ap_dh_ok(int dh) { return dh == 16 || dh == 32 || dh == 64 || dh == 128; }
+
+// the cross-attention kernels (attn_cross.hip): K and V of the SOURCE are what is resident, so the forward and the
+// backward's query launch take ap_fwd_smem(S, dh) / ap_bwd_smem(S, dh) whatever L; the backward's key launch passes Q
+// and dO through LDS AP_QT queries at a time
+static inline size_t ax_bwd_kv_smem(int dh) { return (size_t)2 * AP_QT * (dh + 4) * sizeof(float); }
+// keys of the cached decode step: four waves' score strips of S floats stay inside the default 64 KiB
+#define AX_DEC_SMAX 2048
 
 // the causal kernels: K and V of the head at pitch dh + 1, per-wave probability rows, the chunk's q / dO rows
 static inline size_t ac_fwd_smem(int L, int dh) {

@@ -163,6 +163,7 @@ class CfgProcessor:
         cfg.mdl.setdefault("gpt2_decode_matmul", "fp32")
         cfg.mdl.setdefault("rob_dropout", 0.0)
         cfg.mdl.setdefault("rob_matmul", "fp32")
+        cfg.mdl.setdefault("txed_src", "prompt")
         for k, v in (("sampling", False), ("sampling_topk", -1), ("sampling_topp", -1.0), ("seed", 1)):
             cfg.gen.setdefault(k, v)
         return cfg

@@ -5,7 +5,7 @@ outside it raise NotImplementedError exactly like an unknown name does upstream
 (:46,71,73).
 """
 from .mdl_sf_base import (SFBase, SFBase_TxEnc, LossB, LossLambda, SFPreFeats_TxDec, SFPreFeats_TxEncDec,
-                          Simple_GPT2_New, Simple_TxDec)
+                          Simple_GPT2_New, Simple_TxDec, Simple_TxEncDec)
 from .mdl_evrel import (Simple_EvRel_Roberta, SFPret_SimpleEvRel, SFPret_OnlyVb_SimpleEvRel,
                         SFPret_OnlyVid_SimpleEvRel, Simple_TxEncEvRel)
 from .evl_vsitu import EvalB, EvalB_Acc, EvalB_Gen
@@ -28,6 +28,8 @@ def get_mdl_loss_eval(cfg):
             return {"mdl": Simple_GPT2_New, "loss": LossLambda, "evl": EvalB_Gen}
         if cfg.mdl.mdl_name == "tx_only":
             return {"mdl": Simple_TxDec, "loss": LossLambda, "evl": EvalB_Gen}
+        if cfg.mdl.mdl_name == "txed_only":
+            return {"mdl": Simple_TxEncDec, "loss": LossLambda, "evl": EvalB_Gen}
         if cfg.mdl.mdl_name == "sfpret_txed_vbarg":
             return {"mdl": SFPreFeats_TxDec, "loss": LossLambda, "evl": EvalB_Gen}
         if cfg.mdl.mdl_name == "sfpret_txe_txd_vbarg":

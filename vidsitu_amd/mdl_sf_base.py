@@ -260,27 +260,37 @@ class TxEncoderNew_Conc(TxEncoderOld):
     """mdl_sf_base.py:395-420 (`tx_enc_type: new_conc`): the fairseq-style encoder's output concatenated with
     its input features and mixed by Linear(2d, d)-ReLU-Linear(d, d) (d = 1024 upstream)."""
 
-    def __init__(self, cfg, comm):
-        super().__init__(cfg, comm)
+    _want_embedding = True
+
+    def __init__(self, cfg, comm, text=False):
+        super().__init__(cfg, comm, text=text)
         d = cfg.tx_dec.encoder_embed_dim
         self.orig_tx_out_comb = HipMLP(nn.Linear(2 * d, d), nn.ReLU(), nn.Linear(d, d))
 
     def forward(self, src_tokens=None, src_lengths=None, return_all_hiddens=False, token_embeddings=None):
+        text = token_embeddings is None  # a text encoder: the scaled embeddings take the features' place
         tx_out = super().forward(src_tokens=src_tokens, src_lengths=src_lengths,
                                  return_all_hiddens=return_all_hiddens, token_embeddings=token_embeddings)
         enc_out = tx_out.encoder_out.transpose(0, 1)  # B x T x C
+        if text:
+            token_embeddings = tx_out.encoder_embedding
         enc_out3 = self.orig_tx_out_comb(torch.cat([token_embeddings.float(), enc_out], dim=-1))
-        return EncoderOut(encoder_out=enc_out3.transpose(0, 1).contiguous(), encoder_padding_mask=None,
+        return EncoderOut(encoder_out=enc_out3.transpose(0, 1).contiguous(),
+                          encoder_padding_mask=tx_out.encoder_padding_mask if text else None,
                           encoder_embedding=None, encoder_states=None, src_tokens=None, src_lengths=None)
 
 
-def TxEncoder(cfg, comm):
+def TxEncoder(cfg, comm, text=False):
+    """text: the encoder reads token ids through its own (then trained) embedding table -- the `txed_only` row."""
     if cfg.mdl.tx_enc_type == "new":
+        if text:
+            raise NotImplementedError("tx_enc_type=new takes given embeddings only: a text encoder (mdl_name=txed_only) "
+                                      "needs tx_enc_type 'old' or 'new_conc'")
         return TxEncoderNew(cfg, comm)
     if cfg.mdl.tx_enc_type == "old":  # fairseq TransformerEncoder (SURVEY.md section 8f, row f3)
-        return TxEncoderOld(cfg, comm)
+        return TxEncoderOld(cfg, comm, text=text)
     if cfg.mdl.tx_enc_type == "new_conc":
-        return TxEncoderNew_Conc(cfg, comm)
+        return TxEncoderNew_Conc(cfg, comm, text=text)
     raise NotImplementedError(f"tx_enc_type={cfg.mdl.tx_enc_type}")
 
 
@@ -403,7 +413,7 @@ class Simple_TxDec(nn.Module):
         """Beam search from each event's first token; hypotheses padded into [B, E, 1, longest]."""
         prep = self.prepare_prev_toks_inp(inp)
         prompt = prep["dst_toks"][..., :1]
-        inp["src_tokens"], inp["src_lengths"] = prompt, prep["dst_lens"]
+        inp["src_tokens"], inp["src_lengths"] = self._gen_source(prep)
         hyps = seq_gen._generate(inp, prefix_tokens=prompt)
         best = [h[0]["tokens"] for h in hyps]
         out = prompt.new_full((prompt.size(0), max(len(t) for t in best)), self.pad_index)
@@ -411,6 +421,11 @@ class Simple_TxDec(nn.Module):
             out[row, : len(t)] = t
         b, n_ev = inp["seq_out_by_ev"].shape[:2]
         return out.view(b, n_ev, 1, -1)
+
+
+    def _gen_source(self, prep):
+        """What `forward_gen` hands the search as the source: the one-token prompt (mdl_sf_base.py:660-661)."""
+        return prep["dst_toks"][..., :1], prep["dst_lens"]
 
 
 class Reorderer:
@@ -426,6 +441,39 @@ class Reorderer:
                           encoder_embedding=sel(encoder_out.encoder_embedding, 0),
                           encoder_states=states, src_tokens=sel(encoder_out.src_tokens, 0),
                           src_lengths=sel(encoder_out.src_lengths, 0))
+
+
+class Simple_TxEncDec(Simple_TxDec, Reorderer):
+    """mdl_sf_base.py:678-691 (`txed_only`): a fairseq text encoder over `src_tokens`, the decoder attending over its
+    output.  The reference's loader never supplies `src_tokens` (its training raises KeyError) and its `forward_gen`
+    uses the one-token prompt; `mdl.txed_src` decides the source here, for training and generation alike:
+    'prompt' = the first target token (S = 1, the decoder's per-row constant path), 'vb' = the verb tokens
+    `vb_only_tokens` [B*n_ev, 5] with their padding masked (S = 5, the cross-attention kernels).  A training batch
+    that carries its own `src_tokens` is honoured as is."""
+
+    def build_model(self):
+        super().build_model()
+        src = str(self.cfg.get("txed_src", "prompt"))
+        if src not in ("prompt", "vb"):
+            raise ValueError(f"mdl.txed_src={src!r}: 'prompt' or 'vb'")
+        self.txed_src = src
+        self.encoder = TxEncoder(self.full_cfg, self.comm, text=True)
+        self.use_encoder = True
+
+    def _gen_source(self, prep):
+        if self.txed_src == "vb":
+            vb = prep["vb_only_tokens"].contiguous()
+            return vb, vb.ne(self.pad_index).sum(dim=-1)
+        return super()._gen_source(prep)
+
+    def forward_encoder(self, inp):
+        return self.encoder(inp["src_tokens"], src_lengths=inp["src_lengths"], return_all_hiddens=True)
+
+    def forward(self, inp):
+        if "src_tokens" not in inp:
+            src, lens = self._gen_source(self.prepare_prev_toks_inp(inp))
+            inp = dict(inp, src_tokens=src.contiguous(), src_lengths=lens)
+        return super().forward(inp)
 
 
 class SFPreFeats_TxDec(Simple_TxDec, Reorderer):

@@ -1850,3 +1850,63 @@ def tanh_bwd(dy, y):
     dx = torch.empty_like(dy)
     _lib.call("vs_tanh_bwd", _ptr(dy), _ptr(y), _ptr(dx), dy.numel(), _stream())
     return dx
+
+
+# ---- encoder (cross) attention of the fairseq decoder (csrc/attn_cross.hip) ----------------------
+def attn_cross_fits(l, s, dh, backward):
+    """vs_attn_cross_fits: do the cross-attention kernels hold a source of S keys at head width dh?"""
+    return bool(_lib.load().vs_attn_cross_fits(int(l), int(s), int(dh), int(backward)))
+
+
+def _cross_shapes(what, q, kv, r, l, s, n_head):
+    d = q.shape[1]
+    if q.dim() != 2 or kv.dim() != 2 or q.shape[0] != r * l or tuple(kv.shape) != (r * s, 2 * d) or d % n_head:
+        raise _lib.VsError(f"{what}: q {tuple(q.shape)} / kv {tuple(kv.shape)} are not [{r}*{l}, D] / "
+                           f"[{r}*{s}, 2*D] with D % {n_head} == 0")
+    return d
+
+
+def attn_cross(q, kv, key_mask, r, l, s, n_head):
+    """q f32 [R*L, D], kv f32 [R*S, 2D] (k | v), key_mask uint8 [R, S] (1 = valid) or None -> f32 [R*L, D]."""
+    q, kv = _f32c(q), _f32c(kv)
+    d = _cross_shapes("attn_cross", q, kv, r, l, s, n_head)
+    out = torch.empty((r * l, d), dtype=torch.float32, device=q.device)
+    _lib.call("vs_attn_cross_fwd", _ptr(q), _ptr(kv), _ptr(_key_mask_u8(key_mask, r, s)), _ptr(out), r, l, s, n_head,
+              d // n_head, _stream())
+    return out
+
+
+def attn_cross_bwd(q, kv, key_mask, dout, r, l, s, n_head):
+    """-> (dq [R*L, D], dkv [R*S, 2D]); p is recomputed from q, kv and the mask."""
+    q, kv, dout = _f32c(q), _f32c(kv), _f32c(dout)
+    d = _cross_shapes("attn_cross_bwd", q, kv, r, l, s, n_head)
+    if dout.numel() != r * l * d:
+        raise _lib.VsError("attn_cross_bwd: dout does not match q")
+    dq, dkv = torch.empty_like(q), torch.empty_like(kv)
+    ws = _workspace(_lib.load().vs_attn_cross_bwd_scratch_bytes(r, l, s, n_head), q.device)
+    _lib.call("vs_attn_cross_bwd", _ptr(q), _ptr(kv), _ptr(_key_mask_u8(key_mask, r, s)), _ptr(dout), _ptr(dq),
+              _ptr(dkv), _ptr(ws), C.c_size_t(ws.numel()), r, l, s, n_head, d // n_head, _stream())
+    return dq, dkv
+
+
+def attn_cross_kv_split(kv, kcache, vcache):
+    """kv f32 [rows*S, 2D] -> the decode step's caches f32 [rows, H, S, dh], written in place."""
+    rows, h, s, dh = kcache.shape
+    kv = _f32c(kv)
+    if tuple(kv.shape) != (rows * s, 2 * h * dh) or vcache.shape != kcache.shape or not (
+            kcache.is_contiguous() and vcache.is_contiguous()):
+        raise _lib.VsError("attn_cross_kv_split: kv / cache shapes do not match")
+    _lib.call("vs_attn_cross_kv_split", _ptr(kv), _ptr(kcache), _ptr(vcache), rows, s, h, dh, _stream())
+
+
+def attn_cross_decode(q, kcache, vcache, key_mask, out=None):
+    """One query per (row, head): q f32 [rows, D] against the encoder caches f32 [rows, H, S, dh] -> f32 [rows, D]."""
+    rows, h, s, dh = kcache.shape
+    q = _f32c(q)
+    if tuple(q.shape) != (rows, h * dh) or vcache.shape != kcache.shape or not (
+            kcache.is_contiguous() and vcache.is_contiguous()):
+        raise _lib.VsError("attn_cross_decode: q / cache shapes do not match")
+    out = torch.empty_like(q) if out is None else out
+    _lib.call("vs_attn_cross_decode", _ptr(q), _ptr(kcache), _ptr(vcache), _ptr(_key_mask_u8(key_mask, rows, s)),
+              _ptr(out), rows, s, h, dh, _stream())
+    return out

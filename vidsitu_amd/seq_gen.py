@@ -105,6 +105,13 @@ class _SampleStream:
         self.state.copy_(torch.tensor([self.seed, 0], dtype=torch.long))
 
 
+def _enc_positions(encoder_outs):
+    """Positions of the encoder output [S, rows, d] the decoder attends over; 0 without one."""
+    enc = encoder_outs[0] if encoder_outs else None
+    enc = getattr(enc, "encoder_out", enc)
+    return int(enc.shape[0]) if isinstance(enc, torch.Tensor) and enc.dim() == 3 else 0
+
+
 class _DeviceSearchSession:
     """Static buffers of one generation shape (batch, beam, lengths, vocabulary rules) and, when the
     decoder keeps a KV cache, one hipGraph per step: every kernel argument of a step (position,
@@ -116,7 +123,9 @@ class _DeviceSearchSession:
     def __init__(self, key, dev):
         (self.bsz, self.beam, self.max_len, self.min_len, self.plen, self.V, self.pad, self.eos, self.unk,
          self.unk_penalty, self.temperature, self.normalize, self.len_penalty, self.kv, self.ngram,
-         self.strategy, _) = key  # strategy: None (beam search) or (sampling_topk, sampling_topp)
+         self.strategy, self.src_len, _) = key  # strategy: None (beam search) or (sampling_topk, sampling_topp)
+        # src_len: positions of the encoder output (0 without one) -- the encoder caches `begin_incremental` writes
+        # into the state then have one shape for the session's life, and its captured step graphs stay valid
         bsz, beam, max_len = self.bsz, self.beam, self.max_len
         rows, Lt, Ls = bsz * beam, max_len + 2, max_len + 1
         self.rows, self.Lt, self.Ls = rows, Lt, Ls
@@ -356,7 +365,7 @@ class SeqGenCustom(nn.Module):
         key = (bsz, self.beam_size, max_len, self.min_len, plen, self.vocab_size, self.pad, self.eos,
                self.unk, float(self.unk_penalty), float(self.temperature), bool(self.normalize_scores),
                float(self.len_penalty), bool(self.use_kv_cache), self.no_repeat_ngram_size, self._strategy_key(),
-               str(dev))
+               _enc_positions(encoder_outs), str(dev))
         cache = dec.__dict__.setdefault("_vs_search_sessions", {})
         ses = cache.pop(key, None)
         if ses is None:

@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from gpu_utils import assert_close, rb, to_act, to_w
+from partials_guard import guarded_partials  # noqa: F401  (the row-guard fixture, shared with test_gpu_stem_edges.py)
 from vidsitu_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -43,32 +44,6 @@ CASES = [
     ("stem_slow", 1, 8, 2, 32, 32, 64, (1, 7, 7), (1, 2, 2), (0, 3, 3)),
     ("stem_fast", 1, 8, 8, 32, 32, 8, (5, 7, 7), (1, 2, 2), (2, 3, 3)),
 ]
-
-
-@pytest.fixture
-def guarded_partials(monkeypatch):
-    """A rows query and the launch it sizes a buffer for choose the same kernel.  Every [rows, 2, C] buffer of per-block
-    partials that ops allocates from a rows query during the test (forward BN statistics, BN-backward sums of one or
-    two units, apply on load) becomes the front of a NaN-filled buffer four rows longer.  At the end every float of
-    the `rows` rows has been written and the four rows behind them are still NaN: a launch that chose another kernel
-    than the query writes more rows or fewer.  The guard rows hold an overrun of up to four rows inside the allocation and
-    show any longer one by its first four rows; they do not contain it (a 128-row tile kernel behind a query that
-    answered for 256-row tiles writes twice the rows)."""
-    from vidsitu_amd import ops
-
-    made = []
-
-    def partials(rows, c, device):
-        full = torch.full((rows + 4, 2, c), float("nan"), dtype=torch.float32, device=device)
-        made.append((full, rows))
-        return full[:rows]
-
-    monkeypatch.setattr(ops, "_partials", partials)
-    yield made
-    assert made, "the test allocated no partials"
-    for i, (full, rows) in enumerate(made):
-        assert not bool(torch.isnan(full[:rows]).any()), f"partials {i}: not every one of the {rows} rows was written"
-        assert bool(torch.isnan(full[rows:]).all()), f"partials {i}: the launch wrote past the {rows} rows of the query"
 
 
 def _mk(case, seed=0):

@@ -605,6 +605,24 @@ static size_t stem_smem(int CP, int kT) {
   return w + patch + (size_t)128 * CP * 4 + (size_t)2 * 4 * CP * 4;
 }
 
+#define ST_LDS_MAX (160 * 1024)  // the dynamic LDS size the forward kernels opt in to
+
+// Weight-gradient arms that are instantiated: MT = padded Cout / 16, per kT.
+static bool stem_wg_arm(int MT, int kT) {
+  if (MT == 1 || MT == 2) return true;
+  return (MT == 3 || MT == 4) && (kT == 1 || kT == 3);
+}
+
+// The (Cout, kT) pairs both entry points run (ops.stem_supported states the same set): whichever forward kernel
+// the shape and VS_STEM_PAIR pick fits the LDS opt-in, and the weight gradient has an arm.
+static bool stem_supported(int Cout, int kT) {
+  if (Cout % 8 || Cout < 8 || Cout > 64 || !(kT == 1 || kT == 3 || kT == 5)) return false;
+  const int CP = (Cout + 15) / 16 * 16;
+  if (stem_smem(CP, kT) > ST_LDS_MAX) return false;
+  if (Cout == 8 && kT >= 3 && stem_pair_smem(kT) > ST_LDS_MAX) return false;
+  return stem_wg_arm(CP / 16, kT);
+}
+
 extern "C" int vs_stem_stats_rows(int N, int T, int H, int W) {
   const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
   return N * T * ((Ho + ST_TH - 1) / ST_TH) * ((Wo + ST_TW - 1) / ST_TW);
@@ -614,8 +632,11 @@ extern "C" int vs_stem_conv_fwd(const void* x4, const void* wp, void* y, int N, 
                                 int Cout, int kT, int y_ld, int flags, const float* scale,
                                 const float* shift, float* stats_partial, void* stream) {
   VS_CHECK_ARG(x4 && wp && y, "null tensor");
-  VS_CHECK_ARG(Cout % 8 == 0 && Cout <= 64 && y_ld % 8 == 0 && y_ld >= Cout, "Cout in {8..64}, pitch % 8");
+  VS_CHECK_ARG(N >= 1 && T >= 1 && H >= 1 && W >= 1, "empty input");
+  VS_CHECK_ARG(Cout % 8 == 0 && Cout >= 8 && Cout <= 64 && y_ld % 8 == 0 && y_ld >= Cout,
+               "Cout in {8..64}, pitch % 8");
   VS_CHECK_ARG(kT == 1 || kT == 3 || kT == 5, "kT in {1,3,5}");
+  VS_CHECK_ARG(stem_supported(Cout, kT), "no stem kernel for this (Cout, kT)");
   VS_CHECK_ARG(!(flags & VS_CONV_AFFINE) || (scale && shift), "AFFINE needs scale/shift");
   VS_CHECK_ARG(!(flags & VS_CONV_STATS) || stats_partial, "STATS needs stats_partial");
   VS_CHECK_ARG(!(flags & VS_CONV_RESIDUAL), "no residual on a stem");
@@ -650,7 +671,7 @@ extern "C" int vs_stem_conv_fwd(const void* x4, const void* wp, void* y, int N, 
   if (pair_on && Cout == 8 && kT >= 3 && T >= 2) {  // two output frames per pass (fast-pathway stem)
     static bool attr_done = false;
     if (!attr_done) {
-      (void)hipFuncSetAttribute((const void*)stem_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      (void)hipFuncSetAttribute((const void*)stem_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS_MAX);
       attr_done = true;
     }
     p.tchunks = (T + SP_TC - 1) / SP_TC;
@@ -667,7 +688,7 @@ extern "C" int vs_stem_conv_fwd(const void* x4, const void* wp, void* y, int N, 
     static bool attr_done = false;                                                               \
     if (!attr_done) {                                                                            \
       (void)hipFuncSetAttribute((const void*)stem_conv_kernel<NT_>,                              \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);         \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS_MAX);         \
       attr_done = true;                                                                          \
     }                                                                                            \
     hipLaunchKernelGGL((stem_conv_kernel<NT_>), dim3(grid), dim3(256), smem, st, p);             \
@@ -1012,8 +1033,14 @@ extern "C" int vs_stem_conv_wgrad(const void* dy, const void* x4, float* dwp, in
                                   int W, int Cout, int kT, int dy_ld, void* workspace,
                                   size_t ws_bytes, void* stream) {
   VS_CHECK_ARG(dy && x4 && dwp && workspace, "null tensor");
-  VS_CHECK_ARG(Cout % 8 == 0 && Cout <= 64 && dy_ld % 8 == 0 && dy_ld >= Cout, "Cout in {8..64}, pitch % 8");
+  VS_CHECK_ARG(N >= 1 && T >= 1 && H >= 1 && W >= 1, "empty input");
+  VS_CHECK_ARG(Cout % 8 == 0 && Cout >= 8 && Cout <= 64 && dy_ld % 8 == 0 && dy_ld >= Cout,
+               "Cout in {8..64}, pitch % 8");
   VS_CHECK_ARG(kT == 1 || kT == 3 || kT == 5, "kT in {1,3,5}");
+  if (!stem_supported(Cout, kT)) {
+    vs_set_error("vs_stem_conv_wgrad: unsupported (Cout, kT) = (%d, %d)", Cout, kT);
+    return VS_ERR_UNSUPPORTED;
+  }
   StemWgP p;
   p.x = (const uint16_t*)x4;
   p.dy = (const uint16_t*)dy;
@@ -1060,10 +1087,7 @@ extern "C" int vs_stem_conv_wgrad(const void* dy, const void* x4, float* dwp, in
   else if (MTv == 4 && ntw == 4) LAUNCH_SWG(4, 4);
   else if (MTv == 4 && ntw == 11) LAUNCH_SWG(4, 11);
   else if (MTv == 3 && ntw == 4) LAUNCH_SWG(3, 4);
-  else {
-    vs_set_error("vs_stem_conv_wgrad: unsupported (Cout, kT) = (%d, %d)", Cout, kT);
-    return VS_ERR_UNSUPPORTED;
-  }
+  else LAUNCH_SWG(3, 11);  // stem_supported admitted nothing else
 #undef LAUNCH_SWG
   VS_CHECK_LAUNCH();
   const long long n = (long long)Cout * kT * 7 * 32;

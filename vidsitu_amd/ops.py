@@ -276,6 +276,25 @@ def pack_stem_weight(w, out=None):
     return out
 
 
+STEM_LDS_MAX = 160 * 1024  # dynamic LDS the stem forward kernels opt in to (ST_LDS_MAX in conv_stem.hip)
+_STEM_WGRAD_ARMS = {(mt, kt) for mt in (1, 2) for kt in (1, 3, 5)} | {(mt, kt) for mt in (3, 4) for kt in (1, 3)}
+
+
+def stem_supported(cout, kt):
+    """The (Cout, kT) pairs vs_stem_conv_fwd and vs_stem_conv_wgrad both run; each refuses every other pair with an
+    argument check, before any launch (stem_supported in conv_stem.hip states the same set).  Cout in multiples of 8
+    up to 64, kT in {1, 3, 5}, the forward kernel's LDS (whole packed weight + frame ring + fp32 epilogue tile +
+    statistics scratch: stem_smem) within the opt-in, and an instantiated weight-gradient arm (MT = padded Cout / 16)."""
+    if cout % 8 or not 8 <= cout <= 64 or kt not in (1, 3, 5):
+        return False
+    cp = (cout + 15) // 16 * 16
+    # every term is a multiple of 16 bytes, as the kernels' carve-up needs
+    lds = cp * (kt * 7 * 64 + 16) + kt * 21 * 320 + 128 * cp * 4 + 2 * 4 * cp * 4
+    if cout == 8 and kt >= 3:  # stem_pair_kernel (VS_STEM_PAIR=2): stem_pair_smem
+        lds = max(lds, 16 * ((kt + 1) * 7 * 64 + 16) + (kt + 1) * 37 * 320 + 256 * 16 * 4 + 2 * 8 * 16 * 4)
+    return lds <= STEM_LDS_MAX and (cp // 16, kt) in _STEM_WGRAD_ARMS
+
+
 def stem_conv_fwd(x4, wp, cout, kt, out=None, scale=None, shift=None, relu=False, stats=False):
     """Conv3d(3->cout,[kt,7,7],s[1,2,2],p[kt//2,3,3]) on the C=4 packed input.
     Returns (y, partials|None)."""
@@ -290,7 +309,7 @@ def stem_conv_fwd(x4, wp, cout, kt, out=None, scale=None, shift=None, relu=False
     partials = None
     if stats:
         rows = _lib.load().vs_stem_stats_rows(n, t, h, w)
-        partials = torch.empty((rows, 2, cout), dtype=torch.float32, device=x4.device)
+        partials = _partials(rows, cout, x4.device)
     _lib.call("vs_stem_conv_fwd", _ptr(x4), _ptr(wp), _ptr(out), n, t, h, w, cout, kt, act_ld(out),
               flags, _ptr(scale), _ptr(shift), _ptr(partials), _stream())
     return out, partials

@@ -59,11 +59,9 @@ class Conv3dP(nn.Module):
         self.w_bf16 = None  # [Cout, cin_pad, k] channels-last, refreshed by the trunk
         self.wt_bf16 = None  # transposed image for dgrad
         # the two stems (Cin = 3, [kT,7,7], stride [1,2,2]) run on the dedicated kernel
-        cp = (cout + 15) // 16 * 16
-        stem_lds = cp * (self.k[0] * 7 * 64 + 16) + self.k[0] * 21 * 320 + 128 * cp * 4 + 32 * cp
+        # (ops.stem_supported: the (Cout, kT) pairs both stem entry points run -- whole packed weight in LDS, Cout % 8)
         self.is_stem = (cin == 3 and self.k[1:] == (7, 7) and self.s == (1, 2, 2)
-                        and self.p == (self.k[0] // 2, 3, 3) and cout <= 64
-                        and stem_lds <= 150 * 1024)  # whole packed weight must sit in LDS
+                        and self.p == (self.k[0] // 2, 3, 3) and ops.stem_supported(cout, self.k[0]))
         self.w_stem = None
 
     def refresh(self):

@@ -785,6 +785,22 @@ int vs_sample_step(const float* row_val, const int64_t* row_idx, const int64_t* 
                    int64_t* reorder, const int32_t* anc_in, int32_t* anc_out, int anc_ld, int bsz, int beam,
                    int step, int max_len, int eos, int normalize, float len_penalty, void* stream);
 
+/* vs_beam_step for a diverse beam search (fairseq DiverseBeamSearch / DiverseSiblingsSearch restated;
+ * docs/beam_search_parity.md, "Diverse beam search"), on the same lists with k == 2*beam <= V - 1 (beam <= 32).
+ * groups >= 1 (sibling_rate == 0): beams g, g + groups, ... are group g (step 0: beam g alone); the groups run in order,
+ * group g keeps its 2*beam/groups best entries by v' = fl32(v - fl32(strength * cnt[token])), cnt = the candidates of
+ * the groups before that carry the token (-inf ones included), ties -> lowest beam*V+token; its j-th best is candidate
+ * j*groups + g with score v'.  groups == 1, strength 0 is vs_beam_step bit for bit.  groups == 0: sibling diversity,
+ * step 0 as vs_beam_step, later entry r of a row's list competes as v' = fl32(v - fl32((r + 1) * sibling_rate)) in one
+ * merge over all beams.  The 2*beam candidates are not sorted again; from finalize_hypos on it is vs_beam_step's code.
+ * Refused: beam % groups != 0, k != 2*beam, 2*beam > V - 1, a negative strength or rate. */
+int vs_beam_diverse_step(const float* row_val, const int64_t* row_idx, const int64_t* tok_in, int64_t* tok_out,
+                         const float* sc_in, float* sc_out, uint8_t* ignore, uint8_t* finished, int* nfin,
+                         int* remaining, int64_t* fin_tok, float* fin_score, float* fin_pos, int* fin_len,
+                         int64_t* reorder, const int32_t* anc_in, int32_t* anc_out, int anc_ld, int bsz, int beam,
+                         int k, int V, int step, int max_len, int eos, int normalize, float len_penalty, int groups,
+                         float strength, float sibling_rate, void* stream);
+
 /* Non-local block pieces (slowfast nonlocal_helper.Nonlocal of the i3d_r50_nl_8x8 feature model,
  * Kinetics_c2_I3D_NLN_8x8_R50.yaml:25-28): MaxPool3d([1,2,2], stride [1,2,2]) of a channels-last bf16
  * activation [NT][H][W][C] with a byte argmax per element (0..3 = (dh, dw), first maximum wins) and its

@@ -207,6 +207,7 @@ SIGNATURES = {
     "vs_sample_token": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _i, _i, _i, _d, _i, _i, _i, _f, _f, _i, _p,
                              _sz, _p]),
     "vs_sample_step": (_i, [_p] * 17 + [_i] * 7 + [_f, _p]),
+    "vs_beam_diverse_step": (_i, [_p] * 17 + [_i] * 9 + [_f, _i, _f, _f, _p]),
     "vs_gelu_new_fwd": (_i, [_p, _p, _i64, _p]),
     "vs_gelu_new_bwd": (_i, [_p, _p, _p, _i64, _p]),
     "vs_add_f32": (_i, [_p, _p, _p, _i64, _p]),

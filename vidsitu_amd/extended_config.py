@@ -164,7 +164,8 @@ class CfgProcessor:
         cfg.mdl.setdefault("rob_dropout", 0.0)
         cfg.mdl.setdefault("rob_matmul", "fp32")
         cfg.mdl.setdefault("txed_src", "prompt")
-        for k, v in (("sampling", False), ("sampling_topk", -1), ("sampling_topp", -1.0), ("seed", 1)):
+        for k, v in (("sampling", False), ("sampling_topk", -1), ("sampling_topp", -1.0), ("seed", 1),
+                     ("diverse_beam_groups", -1), ("diverse_beam_strength", 0.5), ("diversity_rate", -1.0)):
             cfg.gen.setdefault(k, v)
         return cfg
 

@@ -1610,6 +1610,19 @@ def sample_step(row_val, row_idx, tok_in, tok_out, sc_in, sc_out, ignore, finish
               float(len_penalty), _stream())
 
 
+def beam_diverse_step(row_val, row_idx, tok_in, tok_out, sc_in, sc_out, ignore, finished, nfin, remaining,
+                      fin_tok, fin_score, fin_pos, fin_len, reorder, bsz, beam, k, vocab, step, max_len, eos,
+                      normalize, len_penalty, groups, strength, sibling_rate, anc_in=None, anc_out=None):
+    """`beam_step` of a diverse beam search (vs_beam_diverse_step): groups >= 1 with a strength, or groups == 0 with a
+    sibling rate; the candidates come group by group, interleaved, and are not sorted again."""
+    anc_ld = 0 if anc_in is None else anc_in.shape[1]
+    _lib.call("vs_beam_diverse_step", _ptr(row_val), _ptr(row_idx), _ptr(tok_in), _ptr(tok_out), _ptr(sc_in),
+              _ptr(sc_out), _ptr(ignore), _ptr(finished), _ptr(nfin), _ptr(remaining), _ptr(fin_tok),
+              _ptr(fin_score), _ptr(fin_pos), _ptr(fin_len), _ptr(reorder), _ptr(anc_in), _ptr(anc_out),
+              int(anc_ld), int(bsz), int(beam), int(k), int(vocab), int(step), int(max_len), int(eos),
+              int(bool(normalize)), float(len_penalty), int(groups), float(strength), float(sibling_rate), _stream())
+
+
 def xent_ignore(logits, labels, ignore_index):
     """Mean CE over rows whose label != ignore_index -> (loss 0-dim, count)."""
     logits = _f32c(logits)

@@ -25,8 +25,14 @@ best first).  Differences, all deliberate:
   drawn on the device (`vs_sample_token`) from the generator of csrc/dropout_rng.h, candidate c of a sentence is
   (parent beam c, row c's draw), and the bookkeeping from `finalize_hypos` on is the beam search's
   (`vs_sample_step`).  Setting both knobs is refused (fairseq silently prefers top-p).  The draws' [seed, step] state
-  lives with the decoder, so the `SeqGenCustom` of every batch continues one stream; `reseed` restarts it.  Any
-  other strategy object raises.
+  lives with the decoder, so the `SeqGenCustom` of every batch continues one stream; `reseed` restarts it;
+* or a `DiverseBeamSearch` / `DiverseSiblingsSearch` (fairseq `--diverse-beam-groups` / `--diverse-beam-strength`,
+  `--diversity-rate`; restated, parity unpinned -- docs/beam_search_parity.md, "Diverse beam search"), or the kwargs
+  `diverse_beam_groups` / `diverse_beam_strength` / `diversity_rate` build one: the scoring pass and its per-row
+  top-2*beam lists are the beam search's, the candidates are formed group by group with a penalty per token the
+  groups before chose (or with a penalty per rank in a row's list) in `vs_beam_diverse_step`, and the step ends in
+  the beam search's bookkeeping.  Sampling, groups and siblings exclude each other.  Any other strategy object
+  raises.
 """
 import math
 
@@ -90,6 +96,30 @@ class Sampling:
             raise ValueError("sampling_topk and sampling_topp exclude each other (fairseq silently prefers top-p)")
 
 
+class DiverseBeamSearch:
+    """fairseq `search.DiverseBeamSearch` by its attribute names: `num_groups` groups of beam / num_groups beams, a
+    token costs `diversity_strength` per candidate of an earlier group that carries it."""
+
+    def __init__(self, tgt_dict=None, num_groups=1, diversity_strength=0.5):
+        self.tgt_dict = tgt_dict
+        self.num_groups, self.diversity_strength = int(num_groups), float(diversity_strength)
+        if self.num_groups < 1:
+            raise ValueError("num_groups must be >= 1")
+        if not self.diversity_strength >= 0.0:
+            raise ValueError("diversity_strength must be >= 0: the per-row lists suffice only for penalties that lower "
+                             "scores (fairseq stores its negative; pass the magnitude)")
+
+
+class DiverseSiblingsSearch:
+    """fairseq `search.DiverseSiblingsSearch`: entry r of a beam's list costs (r + 1) * `diversity_rate`."""
+
+    def __init__(self, tgt_dict=None, diversity_rate=0.5):
+        self.tgt_dict = tgt_dict
+        self.diversity_rate = float(diversity_rate)
+        if not self.diversity_rate >= 0.0:
+            raise ValueError("diversity_rate must be >= 0")
+
+
 class _SampleStream:
     """The [seed, step] state of a decoder's sampling searches (device int64 [2], vs_dropout_tick advances it once
     per search step -- inside the step's graph when steps are captured, so replays draw anew)."""
@@ -123,7 +153,10 @@ class _DeviceSearchSession:
     def __init__(self, key, dev):
         (self.bsz, self.beam, self.max_len, self.min_len, self.plen, self.V, self.pad, self.eos, self.unk,
          self.unk_penalty, self.temperature, self.normalize, self.len_penalty, self.kv, self.ngram,
-         self.strategy, self.src_len, _) = key  # strategy: None (beam search) or (sampling_topk, sampling_topp)
+         self.strategy, self.src_len, _) = key  # strategy: `SeqGenCustom._strategy_key`
+        # None: beam search; (sampling_topk, sampling_topp); ("groups", G, strength) / ("siblings", rate)
+        self.diverse = self.strategy if self.strategy is not None and isinstance(self.strategy[0], str) else None
+        self.sampling = self.strategy is not None and self.diverse is None
         # src_len: positions of the encoder output (0 without one) -- the encoder caches `begin_incremental` writes
         # into the state then have one shape for the session's life, and its captured step graphs stay valid
         bsz, beam, max_len = self.bsz, self.beam, self.max_len
@@ -145,7 +178,7 @@ class _DeviceSearchSession:
         self.reorder = torch.empty(rows, dtype=i64, device=dev)
         self.prefix = torch.empty((bsz, self.plen), dtype=i64, device=dev) if self.plen else None
         self.k = min(2 * beam, beam * self.V - 1, self.V - 1)
-        self.snap = torch.empty(2, dtype=i64, device=dev) if self.strategy is not None else None
+        self.snap = torch.empty(2, dtype=i64, device=dev) if self.sampling else None
         self.state = None
         if self.kv:
             self.state = KVCacheState()
@@ -187,7 +220,7 @@ class _DeviceSearchSession:
             ban_eos = True
         cum = None if step == 0 else self.sc[cur][:, step - 1].contiguous()
         anc_in, anc_out = (self.anc[cur], self.anc[1 - cur]) if self.anc is not None else (None, None)
-        if self.strategy is not None:
+        if self.sampling:
             ops.dropout_tick(self.draw_state, out=self.snap)
             row_val, row_idx = ops.sample_token(logits, cum, forced, self.snap, self.pad, self.eos, self.unk,
                                                 self.strategy[0], self.strategy[1], self.unk_penalty,
@@ -203,6 +236,15 @@ class _DeviceSearchSession:
                                          eos_only=step >= self.max_len, ban_eos=ban_eos,
                                          tokens=self.tok[cur], step=step,
                                          no_repeat_ngram_size=self.ngram)
+        if self.diverse is not None:
+            groups, strength, rate = ((self.diverse[1], self.diverse[2], 0.0) if self.diverse[0] == "groups"
+                                      else (0, 0.0, self.diverse[1]))
+            ops.beam_diverse_step(row_val, row_idx, self.tok[cur], self.tok[1 - cur], self.sc[cur], self.sc[1 - cur],
+                                  self.ignore, self.finished, self.nfin, self.remaining, self.fin_tok,
+                                  self.fin_score, self.fin_pos, self.fin_len, self.reorder, self.bsz, self.beam,
+                                  self.k, self.V, step, self.max_len, self.eos, self.normalize, self.len_penalty,
+                                  groups, strength, rate, anc_in=anc_in, anc_out=anc_out)
+            return
         ops.beam_step(row_val, row_idx, self.tok[cur], self.tok[1 - cur], self.sc[cur], self.sc[1 - cur],
                       self.ignore, self.finished, self.nfin, self.remaining, self.fin_tok, self.fin_score,
                       self.fin_pos, self.fin_len, self.reorder, self.bsz, self.beam, self.k, self.V, step,
@@ -222,7 +264,7 @@ class _DeviceSearchSession:
         # the draws' state is resolved here, before any step: this is where a generator that names another seed
         # restarts the stream (a host-to-device copy, not allowed under capture, and a replayed step runs no Python).
         # One stream per decoder and device, never replaced, so the address the step graphs hold stays the state's
-        self.draw_state = gen.sample_stream(self.tok[0].device).state if self.strategy is not None else None
+        self.draw_state = gen.sample_stream(self.tok[0].device).state if self.sampling else None
         self._reset(prefix_tokens, bos_token)
         if self.state is not None and hasattr(dec, "begin_incremental"):
             # per-generation constants (encoder attention) into the state's static buffers, eagerly
@@ -266,7 +308,8 @@ class SeqGenCustom(nn.Module):
                  normalize_scores=True, len_penalty=1.0, unk_penalty=0.0, temperature=1.0,
                  match_source_len=False, no_repeat_ngram_size=0, search_strategy=None, eos=None,
                  symbols_to_strip_from_output=None, lm_model=None, lm_weight=1.0, use_kv_cache=True,
-                 device_search=True, sampling=False, sampling_topk=-1, sampling_topp=-1.0, seed=1):
+                 device_search=True, sampling=False, sampling_topk=-1, sampling_topp=-1.0, seed=1,
+                 diverse_beam_groups=-1, diverse_beam_strength=0.5, diversity_rate=-1.0):
         super().__init__()
         self.model = models if isinstance(models, EnsembleModel) else EnsembleModel(models)
         self.tgt_dict = tgt_dict
@@ -280,13 +323,35 @@ class SeqGenCustom(nn.Module):
         assert temperature > 0, "--temperature must be greater than 0"
         if match_source_len or lm_model is not None:
             raise NotImplementedError("option unused by the reference's configs (configs/vsitu_cfg.yml:76-85)")
-        if search_strategy is not None and not isinstance(search_strategy, Sampling):
-            raise NotImplementedError("search_strategy: only None (beam search) and Sampling are implemented")
+        if search_strategy is not None and not isinstance(search_strategy, (Sampling, DiverseBeamSearch,
+                                                                            DiverseSiblingsSearch)):
+            raise NotImplementedError("search_strategy: only None (beam search), Sampling, DiverseBeamSearch and "
+                                      "DiverseSiblingsSearch are implemented")
+        # fairseq: "--sampling, --diverse-beam-groups and --diversity-rate are mutually exclusive"; -1 / -1.0 is off
+        asked = [bool(sampling) or isinstance(search_strategy, Sampling),
+                 diverse_beam_groups > 0 or isinstance(search_strategy, DiverseBeamSearch),
+                 diversity_rate > 0 or isinstance(search_strategy, DiverseSiblingsSearch)]
+        if sum(asked) > 1:
+            raise ValueError("sampling, diverse_beam_groups and diversity_rate exclude each other")
+        if diverse_beam_groups not in (-1, 0) and diverse_beam_groups < 1:
+            raise ValueError("diverse_beam_groups must be -1 (off) or >= 1")
+        if diversity_rate != -1.0 and diversity_rate < 0:
+            raise ValueError("diversity_rate must be -1.0 (off) or >= 0")
         if search_strategy is None and sampling:
             search_strategy = Sampling(tgt_dict, sampling_topk, sampling_topp)
         elif search_strategy is None and (sampling_topk != -1 or sampling_topp != -1.0):
             raise ValueError("sampling_topk / sampling_topp need sampling=True")
+        elif search_strategy is None and diverse_beam_groups > 0:
+            search_strategy = DiverseBeamSearch(tgt_dict, diverse_beam_groups, diverse_beam_strength)
+        elif search_strategy is None and diversity_rate > 0:
+            search_strategy = DiverseSiblingsSearch(tgt_dict, diversity_rate)
         self.search = search_strategy  # None: beam search
+        if isinstance(self.search, (DiverseBeamSearch, DiverseSiblingsSearch)):
+            if isinstance(self.search, DiverseBeamSearch) and self.beam_size % self.search.num_groups:
+                raise ValueError(f"beam_size {self.beam_size} is no multiple of the {self.search.num_groups} groups")
+            if self.vocab_size - 1 < 2 * self.beam_size:
+                raise ValueError(f"a diverse beam search needs 2*beam <= V - 1 (beam {self.beam_size}, "
+                                 f"V {self.vocab_size}): its candidates come from the rows' lists of 2*beam tokens")
         self.seed = int(seed)
         if no_repeat_ngram_size < 0 or no_repeat_ngram_size == 1:
             raise NotImplementedError(
@@ -320,6 +385,10 @@ class SeqGenCustom(nn.Module):
         return self._generate_host(sample, prefix_tokens, bos_token)
 
     def _strategy_key(self):
+        if isinstance(self.search, DiverseBeamSearch):
+            return ("groups", self.search.num_groups, self.search.diversity_strength)
+        if isinstance(self.search, DiverseSiblingsSearch):
+            return ("siblings", self.search.diversity_rate)
         return None if self.search is None else (self.search.sampling_topk, self.search.sampling_topp)
 
     def sample_stream(self, dev):
@@ -405,7 +474,8 @@ class SeqGenCustom(nn.Module):
             state.max_len = max_len + 2
         reorder_state = None
         batch_idxs = None
-        if self.search is not None:  # a row draws with the word of its index in the original [bsz * beam] layout
+        sampling = isinstance(self.search, Sampling)
+        if sampling:  # a row draws with the word of its index in the original [bsz * beam] layout
             row_ids = torch.arange(bsz * beam, dtype=torch.long, device=dev)
             stream = self.sample_stream(dev)
 
@@ -429,7 +499,7 @@ class SeqGenCustom(nn.Module):
             elif step < self.min_len:
                 ban_eos = True  # minimum length constraint (does not apply with prefix tokens)
             cum = None if step == 0 else scores[:, step - 1].contiguous()
-            if self.search is not None:
+            if sampling:
                 # Sampling.step: one draw per row, candidate c = (beam c, its draw); no merge, step 0 included
                 val, idx = ops.sample_token(logits, cum, forced, ops.dropout_tick(stream.state), self.pad, self.eos,
                                             self.unk, self.search.sampling_topk, self.search.sampling_topp,
@@ -438,6 +508,9 @@ class SeqGenCustom(nn.Module):
                                             no_repeat_ngram_size=self.no_repeat_ngram_size, row_ids=row_ids)
                 cand_scores, cand_indices = val.view(bsz, beam), idx.view(bsz, beam)
                 cand_beams = torch.arange(beam, device=dev).unsqueeze(0).repeat(bsz, 1)
+            elif self.search is not None:
+                cand_scores, cand_indices, cand_beams = self._diverse_candidates(
+                    logits, cum, forced, k, ban_eos, tokens, step, max_len, bsz)
             else:
                 cand_scores, cand_indices, cand_beams = self._beam_candidates(
                     logits, cum, forced, k, ban_eos, tokens, step, max_len, bsz, cand_size)
@@ -473,7 +546,7 @@ class SeqGenCustom(nn.Module):
                 cands_to_ignore = cands_to_ignore[batch_idxs]
                 scores = scores.view(bsz, -1)[batch_idxs].view(new_bsz * beam, -1)
                 tokens = tokens.view(bsz, -1)[batch_idxs].view(new_bsz * beam, -1)
-                if self.search is not None:
+                if sampling:
                     row_ids = row_ids.view(bsz, beam)[batch_idxs].reshape(-1).contiguous()
                 bsz = new_bsz
             else:
@@ -516,6 +589,44 @@ class SeqGenCustom(nn.Module):
         flat_v = rv.reshape(bsz, beam * k)
         order = torch.sort(flat_v, dim=1, descending=True, stable=True)[1][:, :ncand]
         return flat_v.gather(1, order), ri.reshape(bsz, beam * k).gather(1, order), order // k
+
+    def _diverse_candidates(self, logits, cum, forced, k, ban_eos, tokens, step, max_len, bsz):
+        """The rows' top-2*beam lists and the diverse step on them with torch ops in fp32, the mirror of
+        vs_beam_diverse_step: (scores, tokens, parent beams) [bsz, 2*beam], group g's j-th best at j*G + g."""
+        beam, V = self.beam_size, self.vocab_size
+        row_val, row_idx = ops.beam_topk(logits, cum, forced, k, self.pad, self.eos, self.unk,
+                                         self.unk_penalty, self.temperature,
+                                         eos_only=step >= max_len, ban_eos=ban_eos, tokens=tokens,
+                                         step=step, no_repeat_ngram_size=self.no_repeat_ngram_size)
+        rv, ri = row_val.view(bsz, beam, k), row_idx.view(bsz, beam, k)
+        dev = rv.device
+        siblings = isinstance(self.search, DiverseSiblingsSearch)
+        G = 1 if siblings else self.search.num_groups
+        mb = beam // G
+        if siblings and step > 0:
+            rank = torch.arange(1, k + 1, dtype=torch.float32, device=dev)
+            rv = rv - rank * torch.tensor(self.search.diversity_rate, dtype=torch.float32, device=dev)
+        out_v = torch.empty(bsz, 2 * beam, dtype=torch.float32, device=dev)
+        out_t = torch.empty(bsz, 2 * beam, dtype=torch.long, device=dev)
+        out_b = torch.empty(bsz, 2 * beam, dtype=torch.long, device=dev)
+        for g in range(G):
+            beams = torch.arange(g, g + 1 if step == 0 else beam, G, device=dev)  # step 0: the group's first beam
+            v, t = rv[:, beams, :], ri[:, beams, :]
+            if g > 0:  # tokens of the candidates of the groups before, every one counted
+                prev = out_t.view(bsz, 2 * mb, G)[:, :, :g].reshape(bsz, 1, 1, -1)
+                cnt = (t.unsqueeze(-1) == prev).sum(-1).to(torch.float32)
+                v = v - torch.tensor(self.search.diversity_strength, dtype=torch.float32, device=dev) * cnt
+            n = beams.numel() * k
+            flat_v, flat_t = v.reshape(bsz, n), t.reshape(bsz, n)
+            flat_b = beams.repeat_interleave(k).unsqueeze(0).expand(bsz, n)
+            # value descending, ties towards the lowest beam*V + token: stable sort by the key, then by the value
+            o1 = torch.sort(flat_b * V + flat_t, dim=1, stable=True)[1]
+            o2 = torch.sort(flat_v.gather(1, o1), dim=1, descending=True, stable=True)[1][:, : 2 * mb]
+            order = o1.gather(1, o2)
+            out_v[:, g::G] = flat_v.gather(1, order)
+            out_t[:, g::G] = flat_t.gather(1, order)
+            out_b[:, g::G] = flat_b.gather(1, order)
+        return out_v, out_t, out_b
 
     def finalize_hypos(self, step, bbsz_idx, eos_scores, tokens, scores, finalized, finished,
                        beam_size, max_len):
